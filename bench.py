@@ -11,21 +11,39 @@ fffffff800000000, from start nonce LE64(blake2b(b"start" + LE64(i), 8))
 
 value = Gnonce/s over the whole job = nonces hashed by all ranks (including
 the rest of a chunk after each win) / max over ranks of the timed wall time.
-p50_ttw_ms / max_ttw_ms describe the timed searches; after the timed region
-rank 0 times --latency-searches (default 1,000) more searches on R_0..R_999 at
-the C ABI for a real p50 / p99 of time-to-work (ttw_c_abi_ms), and 100
-work_generate requests over one keep-alive HTTP connection (http_ttw_ms).
+p50_ttw_ms / max_ttw_ms describe the timed searches, ms_per_step is the timed
+wall time / --steps.
+
+A plain run (``--gpus 1 --steps K --warmup W``) does only that: it opens the
+engine, warms up, times the K searches and prints the line.  Everything else the
+search workload measures runs only with ``--full``: the CPU baseline before the
+GPU is opened (cpu_baseline), after the timed region --latency-searches (default
+1,000) more searches on R_0..R_999 at the C ABI for a real p50 / p99 of
+time-to-work (ttw_c_abi_ms, steady_state), 100 work_generate requests over one
+keep-alive HTTP connection (http_ttw_ms), the 8-GPU time regime in a child process
+(node_ttw_8x_regime) and, with several GPUs, the node time-to-work (node_ttw_ms).
+Their options (--no-cpu-baseline, --latency-searches, --http-requests,
+--regime-searches, --node-searches) size or switch off those legs of a --full run.
+
+``--dump-outputs DIR`` (search workload) writes what the last timed search returned
+to its caller as DIR/<name>.npy (float64): status, work_value (the 64-bit value the
+engine returned) and work_value_rehashed (hashlib.blake2b of the returned nonce and
+the root on the CPU -- equal to work_value exactly when the nonce is work for that
+root).  The roots and start nonces depend on the arguments alone, so two builds can
+be compared file for file.  The nonce itself is not written: a first-win search
+returns whichever valid nonce a wave reaches first, so two correct runs may return
+different nonces, while every valid work value lies in [fffffff800000000, 2^64).
 
 Multi-GPU, two ways (``--gpus N``):
   * under ``torch.distributed.run`` (WORLD_SIZE = N, the driver's scaling runs): one rank per GPU,
     every rank searching its own roots on its own GPU (disjoint work, no data-path collective);
     gloo on the CPU carries only the barrier and the max/sum of the timings.  A rank that already
     sees exactly one device (a launcher narrowed HIP_/CUDA_/ROCR_VISIBLE_DEVICES) keeps it; otherwise
-    it takes the LOCAL_RANK-th visible device.  Afterwards every rank searches the same roots on
+    it takes the LOCAL_RANK-th visible device.  With --full, afterwards every rank searches the same roots on
     disjoint strides, the first win cancelling the others through a shared word (node_ttw_ms);
   * in one process (WORLD_SIZE unset, N > 1): the product's own multi-GPU path -- the work pool
     over device_mask = N devices, N searches in flight, each split into N disjoint strides with
-    first-found cancellation across the GPUs (npow_pool.cpp); afterwards one root at a time over
+    first-found cancellation across the GPUs (npow_pool.cpp); with --full, afterwards one root at a time over
     all N (node_ttw_ms, with each search's overshoot: how long the other GPUs kept hashing after the
     host accepted the winner).  Fails if fewer than N devices are visible.
 Scaling is "weak" either way (K searches per GPU).
@@ -38,7 +56,7 @@ kernel runs on (libnanopow stats); peak = 256 CUs x 128 int32 lanes/clk
 achieved rate against 256 x 128 x the in-kernel shader clock of the timed
 launches (s_memtime / s_memrealtime spans of one wave per XCD per launch,
 libnanopow stats clock_mhz).
-cpu_baseline (rank 0, N=1 only, run before the GPU is opened): the reference's
+cpu_baseline (--full; rank 0, N=1 only, run before the GPU is opened): the reference's
 CPU path, hashlib.blake2b(digest_size=8), on every granted host core
 (multiprocessing, disjoint ranges of R_0 from 2^40 at fffffff8, "reference");
 the oracle's C restatement on the same cores and hashlib on one core alongside,
@@ -207,6 +225,17 @@ def bench_root(i: int) -> bytes:
 
 def bench_start(i: int) -> int:
     return int.from_bytes(hashlib.blake2b(b"start" + i.to_bytes(8, "little"), digest_size=8).digest(), "little")
+
+
+def dump_outputs(out_dir: str, root: bytes, status: int, nonce: int, value: int) -> None:
+    """--dump-outputs: what the last timed search returned to its caller, as out_dir/<name>.npy (float64, one
+    element each).  work_value_rehashed is hashlib's value of the returned nonce for that root: the nonce itself
+    differs between correct runs (first win by time), its work value re-hashed on the CPU must equal the engine's."""
+    import numpy as np
+    rehashed = int.from_bytes(hashlib.blake2b(nonce.to_bytes(8, "little") + root, digest_size=8).digest(), "little")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in (("status", status), ("work_value", value), ("work_value_rehashed", rehashed)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.array([float(v)], dtype=np.float64))
 
 
 def pct(xs, p):
@@ -1779,7 +1808,7 @@ def main_inprocess(eng, args) -> int:
     # rates over the time each device hashed: a CU partition that lingered more is not slower
     line["device_check"] = device_check([hash_rate(k) / 1e9 for k in ks], kern_nonces, nonces,
                                         [k.clock_mhz for k in ks])
-    if args.node_searches:
+    if args.full and args.node_searches:
         line["node_ttw_ms"] = inprocess_node_ttw(eng, n, args.node_searches)
     print(json.dumps(line), flush=True)
     if not line["device_check"]["ok"]:
@@ -1795,7 +1824,12 @@ def main() -> int:
                          "N > 1 runs the work pool over N devices in this process")
     ap.add_argument("--steps", type=int, default=300, help="searches per GPU in the timed region")
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="search: also run the legs beside the headline figure (CPU baseline, time-to-work sample, "
+                         "HTTP requests, the 8-GPU time regime child, node time-to-work); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="search, N=1: write what the last timed search returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--iters", type=int, default=0, help="override the search launch iteration cap")
     ap.add_argument("--budget-us", type=int, default=-1, help="override the search launch budget (0 = off)")
     ap.add_argument("--workload", default="search",
@@ -1811,17 +1845,23 @@ def main() -> int:
     ap.add_argument("--via", choices=["abi", "http"], default="abi",
                     help="burst: submit through the C ABI work pool or POST to the HTTP work server")
     ap.add_argument("--node-searches", type=int, default=300,
-                    help="search, N>1: roots searched by all GPUs at once after the timed steps (node time-to-work)")
+                    help="search --full, N>1: roots searched by all GPUs at once after the timed steps (node "
+                         "time-to-work)")
     ap.add_argument("--http-requests", type=int, default=100,
-                    help="search, N=1: work_generate requests timed at the JSON boundary after the timed steps")
+                    help="search --full, N=1: work_generate requests timed at the JSON boundary after the timed steps; "
+                         "regime: requests over one keep-alive connection")
     ap.add_argument("--latency-searches", type=int, default=1000,
-                    help="search, N=1: C-ABI searches on R_0..R_{n-1} after the timed steps (p50/p99 time-to-work)")
+                    help="search --full, N=1: C-ABI searches on R_0..R_{n-1} after the timed steps (p50/p99 "
+                         "time-to-work)")
     ap.add_argument("--regime-searches", type=int, default=500,
-                    help="search, N=1: searches of the 8-GPU time regime run in a child process after the bench "
-                         "(node_ttw_8x_regime; 0 = skip)")
+                    help="search --full, N=1: searches of the 8-GPU time regime run in a child process after the "
+                         "bench (node_ttw_8x_regime; 0 = skip)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs and (args.workload != "search" or WORLD > 1 or args.gpus > 1):
+        raise SystemExit("bench.py: --dump-outputs writes the last result of the search workload on one GPU (with "
+                         "several, which search ends last depends on timing)")
     if WORLD > 1 and args.gpus != WORLD:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={WORLD}: under torch.distributed.run "
                          "there is one rank per GPU")
@@ -1829,7 +1869,7 @@ def main() -> int:
 
     # The CPU legs run first, before anything opens the GPU (their worker processes are forked).
     cpu = None
-    if args.workload == "search" and WORLD == 1 and args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and args.workload == "search" and WORLD == 1 and args.gpus == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
     recv_cpu = receive_cpu_legs(args) if args.workload == "receive" else None
     if cpu or recv_cpu:
@@ -1871,10 +1911,14 @@ def main() -> int:
     if inproc:
         return main_inprocess(eng, args)
 
+    last = []  # the newest search's (root, status, nonce, value): after run_timed, the last timed step's
+
     def search(i):
         # time-to-work at the result (npow_wait_result), nonces after the ticket's collection; the timed
         # region's wall time includes the collection (the next search starts after it)
-        t_res, _t_all, info = search_to_result(eng, bench_root(i), SEND, bench_start(i), 1 << dev)
+        root = bench_root(i)
+        t_res, _t_all, info = search_to_result(eng, root, SEND, bench_start(i), 1 << dev)
+        last[:] = [root, info.status, info.nonce, info.value]
         return t_res, info.nonces_done
 
     timed_stats = []
@@ -1895,8 +1939,10 @@ def main() -> int:
     else:
         gathered = [local]
     kern_rate = res[4] / (res[3] * 1e-3) / 1e9 if res[3] > 0 else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *last)
     lat, lat_clk, steady = None, None, None
-    if WORLD == 1 and args.latency_searches:
+    if args.full and WORLD == 1 and args.latency_searches:
         # the card's clock and power over the ~11-s time-to-work leg too (the timed region is ~0.2 s at the
         # driver's 20 steps: a handful of samples), every 25 ms, with the in-kernel clock of the same launches
         eng.reset_stats(dev)
@@ -1909,9 +1955,9 @@ def main() -> int:
                            "fffffff8 and the receive-difficulty overhead sample) sampled every 25 ms; the in-kernel "
                            "clock of their launches beside"}
         steady = steady_state(lat, leg, lat_sclk, args.latency_searches)
-    http = _http_ttw(eng, args.http_requests) if (rank == 0 and WORLD == 1 and args.http_requests) else None
+    http = _http_ttw(eng, args.http_requests) if (args.full and rank == 0 and WORLD == 1 and args.http_requests) else None
     node = None
-    if dist is not None and args.node_searches > 0 and int(os.environ.get("LOCAL_WORLD_SIZE", WORLD)) == WORLD:
+    if args.full and dist is not None and args.node_searches > 0 and int(os.environ.get("LOCAL_WORLD_SIZE", WORLD)) == WORLD:
         node = node_time_to_work(eng, dev, rank, WORLD, dist, args.node_searches)
     if rank == 0:
         line = result_line(WORLD, args.steps, args.warmup, *res)
@@ -1942,7 +1988,7 @@ def main() -> int:
         if cpu:
             line["cpu_baseline"] = cpu
         line["device_check"] = device_check([g[2] for g in gathered], res[4], res[0], [g[0] for g in gathered])
-        if WORLD == 1 and args.regime_searches:
+        if args.full and WORLD == 1 and args.regime_searches:
             line["node_ttw_8x_regime"] = regime_child(8, args.regime_searches)
         print(json.dumps(line), flush=True)
     rc = 0

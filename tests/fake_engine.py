@@ -52,10 +52,13 @@ class OracleEngine:
     """n_devices > 1 emulates the pool's multi-device split: a search over a mask of G devices runs G
     threads on the disjoint strides start + k * 2^64 / G, the first win stopping the others."""
 
-    def __init__(self, chunk=1 << 12, delay=0.0, n_devices=1):
+    def __init__(self, chunk=1 << 12, delay=0.0, n_devices=1, count_stats=False):
+        """count_stats: a one-device engine keeps its device's nonce / launch counters too (the split path
+        over one stride), as the library does."""
         self.chunk = chunk
         self.delay = delay
         self.n_devices = n_devices
+        self.count_stats = count_stats
         self.calls = []
         self.lock = threading.Lock()
         self._stats = [dict(nonces=0, launches=0, kernel_ms=0.0) for _ in range(n_devices)]
@@ -142,7 +145,7 @@ class OracleEngine:
     def submit(self, root, threshold, start=0, device_mask=0, max_nonces_per_device=0, cancel=None):
         own = _Flag()  # Ticket.cancel() (npow_cancel)
         either = _Either(own, cancel)
-        if self.n_devices > 1 and not max_nonces_per_device:
+        if (self.n_devices > 1 or self.count_stats) and not max_nonces_per_device:
             tk = _Ticket(lambda: self._split(root, threshold, start, device_mask, either))
         else:
             tk = _Ticket(lambda: self.search(root, threshold, start, device_mask, max_nonces_per_device, either))

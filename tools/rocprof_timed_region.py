@@ -2,8 +2,8 @@
 """rocprofv3 kernel trace vs bench.py's own event timing over the timed region.
 
 Usage: python3 tools/rocprof_timed_region.py TRACE_CSV BENCH_JSON KERNEL_SUBSTR [command text]
-Run the bench under `rocprofv3 --kernel-trace --stats` with --latency-searches 0 --http-requests 0
---no-cpu-baseline, so its timed launches are the trace's last `roofline.launches` dispatches of the
+Run the bench under `rocprofv3 --kernel-trace --stats` as a plain run (without --full: no searches
+after the timed steps), so its timed launches are the trace's last `roofline.launches` dispatches of the
 kernel; prints the average dispatch duration of those against the bench's HIP-event average.
 """
 import csv
