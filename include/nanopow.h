@@ -65,8 +65,10 @@ extern "C" {
  * 6: npow_device_stats gains stale_drains / stale_late / stale_missing / stale_gpu_delay_us (won or killed jobs of a
  * lingering launch whose final count had not come 1 ms after their stop; of those, the ones whose count came later and
  * the ones whose count never came -- a protocol check: 0), linger_ms (the device's lingering launches waiting with
- * nothing to hash, inside kernel_ms) and linger_relays (kills relayed by a lingering workgroup). */
-#define NPOW_ABI_VERSION 6
+ * nothing to hash, inside kernel_ms) and linger_relays (kills relayed by a lingering workgroup).
+ * 7: npow_submit_weighted (a job's weight: its share of each GPU among the live searches, and its place in the
+ * admission queue); npow_submit is the same call with weight 1. */
+#define NPOW_ABI_VERSION 7
 
 /* Hash paths of npow_values_path. */
 #define NPOW_PATH_SEARCH 0  /* the instruction stream the search and sweep kernels execute
@@ -232,6 +234,17 @@ int npow_search_batch(const uint8_t* roots, const uint64_t* thresholds, uint32_t
  * status for the ticket. */
 int npow_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
                 uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint64_t* ticket);
+
+/* npow_submit with a weight in {1, 2, 4, 8} (ABI 7); npow_submit is weight 1.  Among the live unbounded searches of
+ * one GPU a job's expected share of the device's workgroups -- and so of its hash rate -- is weight / (sum of the
+ * weights): an on-demand request of weight 8 among 15 precache requests of weight 1 gets 8/23 of the GPU instead of
+ * 1/16.  A job split over several devices carries its weight on each of them; the CPU workers (one job at a time)
+ * ignore it.  Waiting jobs (more than max_active submitted) are admitted heaviest first, first come first served
+ * within a weight.  NPOW_ERR_BAD_ARGUMENT for any other weight, and for a weight above 1 together with
+ * max_nonces_per_device != 0 (a bounded search is covered by its own workgroups only). */
+int npow_submit_weighted(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
+                         uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint32_t weight,
+                         uint64_t* ticket);
 
 /* Wait up to timeout_us (< 0: forever) for a ticket.  Returns NPOW_PENDING on timeout
  * (the ticket stays valid), otherwise the search's final status exactly as npow_search

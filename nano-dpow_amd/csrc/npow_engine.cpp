@@ -696,6 +696,18 @@ int npow_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint
   return pool_submit(root, threshold, start, device_mask, max_nonces_per_device, cancel, ticket);
 } catch (...) { return guard_exception(); }
 
+int npow_submit_weighted(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
+                         uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint32_t weight,
+                         uint64_t* ticket) try {
+  if (int rc = check_init()) return rc;
+  if (!root || !ticket) return fail(NPOW_ERR_BAD_ARGUMENT, "root and ticket are required");
+  if (weight != 1 && weight != 2 && weight != 4 && weight != 8)
+    return fail(NPOW_ERR_BAD_ARGUMENT, "weight must be 1, 2, 4 or 8");
+  if (weight > 1 && max_nonces_per_device != 0)
+    return fail(NPOW_ERR_BAD_ARGUMENT, "a bounded search (max_nonces_per_device) takes weight 1 only");
+  return pool_submit(root, threshold, start, device_mask, max_nonces_per_device, cancel, ticket, weight);
+} catch (...) { return guard_exception(); }
+
 int npow_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce_out, uint64_t* value_out,
               uint64_t* nonces_done) try {
   if (int rc = check_init()) return rc;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "npow_blake2b.h"
+#include "npow_weights.h"
 #include "npow_hash_asm.inc"
 #include "npow_hash_asm_lockstep_ld.inc"
 
@@ -88,7 +89,7 @@ struct alignas(64) HostMailbox {
 // ---- Work pool: many roots searched by one launch (npow_pool_kernel_ls2*) -------------------
 // Each device keeps up to kMaxSlots live jobs in "slots".  Every launch reads a table of
 // the live entries (its kernel arguments, or device memory past kArgEntries entries);
-// workgroup g starts on entry g % n.  A slot is identified per job by a generation number `gen` (unique, > 0): a slot
+// workgroup g starts on entry g % n (or, with weighted jobs, where the start map PoolTable::wsum puts it).  A slot is identified per job by a generation number `gen` (unique, > 0): a slot
 // is dead for generation g once PoolDevState::slot[s].dead >= g (set by its winner with
 // atomicMax, or relayed from the host kill word), so a slot can be reused for a new job
 // with a larger gen without clearing any device memory.
@@ -111,7 +112,13 @@ struct PoolEntry {
   uint64_t gen;
   uint32_t slot;     // device slot index (PoolDevState / PoolMailbox arrays)
   uint32_t bounded;  // 1: dense mapping over the entry's own workgroups, no migrants
+  uint32_t wsh;      // unbounded: 3 - log2(weight), weight in {1, 2, 4, 8} (npow_submit_weighted): wherever two
+                     // entries' workgroup counts are compared, each is shifted left by its wsh first, so a job's
+                     // share of the launch's workgroups is weight / (sum of weights).  Equal values compare as the
+                     // plain counts do (kWshOne everywhere: the unweighted pool)
+  uint32_t pad;
 };
+// (kWshOne, pool_wsh and the table builder's rule pool_table_weights: npow_weights.h)
 static_assert(offsetof(PoolEntry, u) == 0, "the search kernel finds an entry from its uniforms' address");
 struct PoolTable {
   uint32_t n;          // entries in use (1..kMaxSlots)
@@ -135,7 +142,13 @@ struct PoolTable {
                           // waits in the launch for the host's next dynamic entry (ls2_linger) until a yield,
                           // instead of leaving -- the next search needs no launch; the value (a power of two) is
                           // the lingering workgroups' period, in looks, of reading the pinned ctl word
-  uint32_t pad[4];
+  uint32_t wsum;          // search kernels, > 0: the launch's start map (round 7) -- the sum of the table entries'
+                          // weights (8 >> PoolEntry::wsh each): workgroup g starts on the entry whose run of the
+                          // cumulative weights holds pool_start_pos(g, wsum), so a launch begins at its jobs'
+                          // weighted shares.  The host halves a crowded table's weights until a workgroup starts
+                          // on every entry (pool_table_weights, npow_weights.h).  0: g % n (every weight equal, or a table with
+                          // a bounded entry, whose dense mapping needs g % n == e)
+  uint32_t pad[3];
   PoolEntry e[kMaxSlots];
 };
 inline size_t pool_table_bytes(uint32_t n) { return offsetof(PoolTable, e) + (size_t)n * sizeof(PoolEntry); }

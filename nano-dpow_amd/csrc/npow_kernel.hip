@@ -565,17 +565,18 @@ __device__ __forceinline__ ConstEntry* ls2_entry(const PoolTable* tab, const Poo
 // hash does acquire (ls2_choose).
 struct EntryHdr {
   uint64_t gen;
-  uint32_t slot, bounded;
+  uint32_t slot, bounded, wsh;
 };
 __device__ __forceinline__ EntryHdr ls2_hdr(const PoolTable* tab, PoolMailbox* mb, uint32_t e) {
   if (e < tab->n) {
     ConstEntry* q = (ConstEntry*)(uintptr_t)&tab->e[e];
-    return EntryHdr{q->gen, q->slot, q->bounded};
+    return EntryHdr{q->gen, q->slot, q->bounded, q->wsh};
   }
   PoolEntry* q = &mb->dyn[(tab->dyn_base + (e - tab->n)) % kDynRing].e;
   return EntryHdr{__hip_atomic_load(&q->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM),
                   __hip_atomic_load(&q->slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM),
-                  __hip_atomic_load(&q->bounded, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)};
+                  __hip_atomic_load(&q->bounded, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM),
+                  __hip_atomic_load(&q->wsh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)};
 }
 // Relaxed: an acquire at system scope invalidates the L2, which at every poll cost 4x the search
 // kernel's fetches.  But a ring position's lines may still sit in an XCD's L2 from an earlier launch
@@ -627,9 +628,13 @@ __device__ __forceinline__ unsigned long long ls2_wgs(PoolDevState* st, uint32_t
 
 // A polling wave (lane 0 only): the host words of the entry.  Returns bit 0 set when the wave's
 // workgroup must leave the entry, and bit 1 too when the reason is the pinned kill word: new jobs wait and the entry is unbounded (a yield), it was
-// killed, or it is unbounded and a dynamic entry has at least two workgroups fewer than it (the
-// workgroup moves there: a job that joined the running launch collects its share a workgroup at a
-// time, each from the most crowded entry among the pollers).
+// killed, or it is unbounded and a dynamic entry would, with this workgroup on it, still hold no more workgroups
+// than this entry without it -- counts scaled by the entries' weights (count << PoolEntry::wsh; with equal weights:
+// at least two workgroups fewer) -- (the
+// workgroup moves there: a job that joined the running launch collects its weighted share a workgroup at a
+// time, each from the most crowded entry among the pollers).  After such a move the reverse one does not qualify
+// (the destination's scaled count stays below the source's old one), so two entries never trade a workgroup
+// back and forth.
 __device__ __forceinline__ uint32_t ls2_poll(const PoolTable* tab, PoolDevState* st, PoolMailbox* mb, uint32_t e,
                                          uint32_t* seen) {
   const ConstEntry* pe = ls2_entry(tab, mb, e);
@@ -702,7 +707,9 @@ __device__ __forceinline__ uint32_t ls2_poll(const PoolTable* tab, PoolDevState*
         found |= 1ull << k;
         continue;
       }
-      leave = ls2_wgs(st, q.slot) + 2 <= mine;
+      // (q + 1) << wsh_q <= (mine - 1) << wsh_mine, without the subtraction; equal weights: q + 2 <= mine
+      const uint32_t sq = q.wsh & 3u, sm = pe->wsh & 3u;
+      leave = ((ls2_wgs(st, q.slot) + 1) << sq) + (1ull << sm) <= (mine << sm);
     }
     ls2_mark_over(found);
   }
@@ -710,7 +717,7 @@ __device__ __forceinline__ uint32_t ls2_poll(const PoolTable* tab, PoolDevState*
 }
 
 // Wave 0 (every lane): of the launch's first nd dynamic entries and its table's, the live unbounded entry other than e
-// with the fewest workgroups, joined, ties broken by a hash of the workgroup index so that the workgroups leaving one
+// with the fewest workgroups for its weight (the count << PoolEntry::wsh), joined, ties broken by a hash of the workgroup index so that the workgroups leaving one
 // entry spread over the others; kNoEntry if none can be.  Each lane looks at one entry.
 __device__ __forceinline__ uint32_t ls2_choose(const PoolTable* tab, PoolDevState* st, PoolMailbox* mb, uint32_t e,
                                                uint32_t nd, uint32_t* seen, uint32_t lane, uint32_t g) {
@@ -724,7 +731,7 @@ __device__ __forceinline__ uint32_t ls2_choose(const PoolTable* tab, PoolDevStat
       ConstEntry* q = ls2_entry(tab, mb, lane);
       if (!q->bounded && load_dead(st, q->slot) < q->gen) {
         const uint32_t tie = ((lane + 1u) * 0x9e3779b1u) ^ (g * 0x85ebca6bu);
-        key = (ls2_wgs(st, q->slot) << 32) | (tie & ~63u) | lane;
+        key = ((ls2_wgs(st, q->slot) << (q->wsh & 3u)) << 32) | (tie & ~63u) | lane;
       } else {
         over = true;
       }
@@ -832,6 +839,20 @@ __device__ __noinline__ uint32_t ls2_pick(const PoolTable* tab, PoolDevState* st
   // (and spill) the register the ABI passes it in
   const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), g = blockIdx.x;
   if (first) {
+    // the launch's start map (PoolTable::wsum > 0; each lane one table entry): the entry whose run of the cumulative
+    // weights holds pool_start_pos(g, wsum) (npow_weights.h: consecutive workgroups spread over the whole map), i.e.
+    // the number of entries whose inclusive prefix sum is <= it
+    if (tab->wsum) {
+      const uint32_t r = pool_start_pos(g, tab->wsum);
+      uint32_t acc = lane < tab->n ? 8u >> (((ConstEntry*)(uintptr_t)&tab->e[lane])->wsh & 3u) : 0u;
+#pragma unroll
+      for (int m = 1; m < 64; m <<= 1) {
+        const uint32_t o = __shfl_up(acc, m);
+        if (lane >= (uint32_t)m) acc += o;
+      }
+      const uint32_t k = (uint32_t)__builtin_popcountll(__ballot(lane < tab->n && acc <= r));
+      e = k < tab->n ? k : tab->n - 1u;  // (k < n whenever wsum is the weights' sum)
+    }
     uint32_t ok = 0;
     if (lane == 0) {
       ConstEntry* pe = ls2_entry(tab, mb, e);

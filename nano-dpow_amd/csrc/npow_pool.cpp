@@ -625,6 +625,7 @@ struct PoolInflight {
   uint64_t yield_base;  // PoolTable::yield_base of the launch
   bool counted;         // PoolTable::counted: early finish and dynamic entries are on in it
   bool linger;          // PoolTable::linger: its workgroups wait for dynamic entries until its budget or a yield
+  uint32_t wdown;       // its table's weights were halved this many times (pool_table_weights): its dynamic entries' too
 };
 
 class Worker {
@@ -819,6 +820,9 @@ bool Worker::dyn_add(int s) {
   pe.gen = sl.gen;
   pe.slot = (uint32_t)s;
   pe.bounded = 0;
+  // the scaled balancing rule (ls2_poll) moves workgroups here up to its weighted share; on the table's scale
+  pe.wsh = pool_wsh((j.weight >> f.wdown) ? (j.weight >> f.wdown) : 1u);
+  pe.pad = 0;
   Range& r = todo.front();
   pe.base = r.base;
   pe.count = full;
@@ -1151,7 +1155,8 @@ int Worker::launch(bool empty_linger) {
   const PoolShape sh = pool_shape(d_);
   const uint32_t iters = sh.launch_iters(g_iters.load());
   PoolTable& t = *d_.h_tab[ring_];
-  uint32_t n = 0;
+  uint32_t n = 0, wdown = 0;
+  uint32_t weights[kMaxSlots], wshs[kMaxSlots];
   bool bounded = false;
   int idx[kMaxSlots];
   for (int s = 0; s < kMaxSlots; ++s)
@@ -1197,6 +1202,9 @@ int Worker::launch(bool empty_linger) {
       pe.base = r.base;
       pe.count = std::min(want, r.count);
       pe.bounded = (j.max_per_dev || pe.count < full) ? 1 : 0;
+      pe.wsh = pool_wsh(j.weight);
+      pe.pad = 0;
+      weights[e] = j.weight;
       if (pe.bounded) {
         pe.count = std::min(pe.count, own);
         bounded = true;
@@ -1210,6 +1218,16 @@ int Worker::launch(bool empty_linger) {
       if (todo.empty()) sl.no_more = true;
       sl.fresh = false;
     }
+  }
+  // The start map (PoolTable::wsum): workgroup g starts on the entry whose run of the cumulative weights holds
+  // pool_start_pos(g, wsum), so every launch begins at its jobs' weighted shares (the kernel balances only toward
+  // dynamic entries: a table dealt g % n would never reach them).  Equal weights, or a bounded entry (dense over
+  // g % n == e): g % n.  Only differing weights need the map, and a workgroup must start on every entry, or that
+  // entry would stay without one: pool_table_weights (npow_weights.h) halves a crowded table's weights until so.
+  t.wsum = 0;
+  if (!bounded) {
+    t.wsum = pool_table_weights(weights, n, (uint32_t)sh.grid, wshs, &wdown);
+    for (uint32_t e = 0; e < n; ++e) t.e[e].wsh = wshs[e];
   }
   if (lingers(d_) && !bounded && g_budget_us.load() > 0) {
     // each lingering workgroup reads the pinned ctl word once in P looks (phase g): ~2 reads per look grid-wide
@@ -1241,11 +1259,11 @@ int Worker::launch(bool empty_linger) {
   }
   HIPTRY(hipEventRecord(d_.ev_stop[r], d_.stream));
   if (q_.empty()) front_start_ = std::chrono::steady_clock::now();
-  NPOW_DBGT("nanopow[%d]: launch %llu n=%u linger %u yield_base %llx slots:", d_.id, (unsigned long long)seq_, n,
-            t.linger, (unsigned long long)t.yield_base);
+  NPOW_DBGT("nanopow[%d]: launch %llu n=%u linger %u wsum %u (weights halved %u times) yield_base %llx slots:", d_.id,
+            (unsigned long long)seq_, n, t.linger, t.wsum, wdown, (unsigned long long)t.yield_base);
   for (uint32_t e = 0; e < n; ++e) NPOW_DBG(" %d/g%llu", idx[e], (unsigned long long)t.e[e].gen);
   NPOW_DBG("\n");
-  q_.push_back({seq_, r, (uint32_t)ctl_, t.yield_base, t.counted != 0, t.linger != 0});
+  q_.push_back({seq_, r, (uint32_t)ctl_, t.yield_base, t.counted != 0, t.linger != 0, wdown});
   return NPOW_OK;
 }
 
@@ -1780,7 +1798,7 @@ void pool_stop() {
 
 // -- jobs -------------------------------------------------------------------------------------------
 int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
-                uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint64_t* ticket) {
+                uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint64_t* ticket, uint32_t weight) {
   // A bounded search over "all devices" (mask 0) leaves the CPU workers out: their stride would be as
   // long as a GPU's at ~1/1000 of its rate, nothing hands their leftover to an idle GPU, and they work on one job
   // at a time -- an exhausting search would wait for them.  An explicit mask may still name the CPU device.
@@ -1794,6 +1812,7 @@ int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint
   j->start = start;
   j->max_per_dev = max_nonces_per_device;
   j->cancel = cancel;
+  j->weight = max_nonces_per_device ? 1u : weight;
   const uint64_t G = devs.size();
   j->spacing = G > 1 ? (~0ull / G) + 1 : 0;  // 2^64 / G (exact for powers of two)
   for (Device* d : devs) j->devs.push_back(d->id);
@@ -1818,7 +1837,11 @@ int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint
   if (!g_pool.running) return fail(NPOW_ERR_NOT_INITIALISED, "engine is shut down");
   j->ticket = g_pool.next_ticket++;
   g_pool.tickets[j->ticket] = j;
-  g_pool.waiting.push_back(j);
+  // the waiting queue is kept by weight, heaviest first, FIFO within a weight (admit_locked takes its front):
+  // behind the last job at least as heavy.  With every weight 1 this is the back.
+  auto at = g_pool.waiting.end();
+  while (at != g_pool.waiting.begin() && (*(at - 1))->weight < j->weight) --at;
+  g_pool.waiting.insert(at, j);
   admit_locked();
   *ticket = j->ticket;
   return NPOW_OK;

@@ -28,6 +28,8 @@ struct Job {
   uint64_t u[NPOW_ASM_N_UNIFORMS] = {};
   uint64_t threshold = 0, start = 0, max_per_dev = 0, spacing = 0;
   const volatile uint32_t* cancel = nullptr;
+  uint32_t weight = 1;    // 1, 2, 4 or 8 (npow_submit_weighted): its share of each GPU's workgroups among the live
+                          // unbounded jobs, and its place in the admission queue; the CPU device ignores it
   std::vector<int> devs;  // device ids; the k-th starts on [start + k * spacing, + stride)
   // guarded by g_pool.mu
   std::vector<std::deque<Range>> todo;  // per device k: ranges not yet handed to a launch (a dead

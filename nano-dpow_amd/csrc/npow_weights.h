@@ -1,0 +1,66 @@
+// npow_weights.h -- job weights of the work pool as a launch's table carries them (host side; no HIP types, so
+// the table builder's rule can be compiled and checked on its own: tests/test_weights_cpu.py).
+#pragma once
+#include <stdint.h>
+
+namespace npow {
+
+constexpr uint32_t kWshOne = 3;  // PoolEntry::wsh of weight 1
+inline uint32_t pool_wsh(uint32_t weight) {  // weight in {1, 2, 4, 8} -> 3 - log2(weight)
+  return weight >= 8 ? 0u : weight >= 4 ? 1u : weight >= 2 ? 2u : 3u;
+}
+
+// The start map: workgroup g of a launch whose table weights sum to wsum starts on the entry whose run of the
+// cumulative weights holds pool_start_pos(g, wsum) in [0, wsum): the fractional part of g times the golden ratio,
+// scaled.  Any stretch of consecutive workgroup indices is then spread almost evenly over [0, wsum), which matters
+// twice: workgroups are dispatched in index order, four per CU, and a SIMD favours its oldest waves, so the first
+// CUs-many indices hash several times as fast as the last (a map of contiguous runs, g % wsum, gave the first
+// entries of a crowded table all the fast workgroups: measured 7 : 1 between equal jobs on a 32-CU partition); and
+// workgroup counts are balanced per XCD shard (g mod 8), which a modulus sharing a factor with 8 aliases with.
+#if defined(__HIPCC__)
+#define NPOW_HD __host__ __device__
+#else
+#define NPOW_HD
+#endif
+NPOW_HD inline uint32_t pool_start_pos(uint32_t g, uint32_t wsum) {
+  return (uint32_t)(((uint64_t)(uint32_t)(g * 0x9E3779B9u) * wsum) >> 32);
+}
+
+// The weights a launch of `grid` workgroups gives its n unbounded table entries, from the jobs' weights w[0..n)
+// (each 1, 2, 4 or 8): wsh[i] = PoolEntry::wsh of entry i; *down = how many times every weight was halved (the
+// launch's dynamic entries are halved alike, Worker::dyn_add); returns PoolTable::wsum, the start map's modulus,
+// or 0 for the plain g % n start.
+//  * Every weight equal (all 1, but also all 8): g % n deals equal shares exactly, so no map (0); the entries keep
+//    their true wsh, against which a dynamic entry of another weight is compared.
+//  * Otherwise the map above.  An entry on which no workgroup starts would -- the kernel balancing only toward
+//    dynamic entries -- stay without one, launch after launch; with g % n and n <= 64 every entry has one.  So the
+//    builder walks the grid through the map, and while some entry is left empty (a crowded table on a small grid:
+//    a CU partition's is 128, and twenty jobs of weight 8 beside a light one sum to 161) it halves every weight,
+//    floor 1, and tries again.  Halving flattens the ratios between the heaviest and the lightest jobs (8 : 1
+//    becomes 4 : 1), only in tables that crowded.  If the halved weights are all equal, the table is dealt g % n (0).
+inline uint32_t pool_table_weights(const uint32_t* w, uint32_t n, uint32_t grid, uint32_t* wsh, uint32_t* down) {
+  *down = 0;
+  for (uint32_t k = 0;; ++k) {
+    uint32_t sum = 0, prefix[64];
+    bool equal = true;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t eff = (w[i] >> k) ? (w[i] >> k) : 1u;
+      wsh[i] = pool_wsh(eff);
+      sum += eff;
+      if (i < 64) prefix[i] = sum;
+      equal = equal && wsh[i] == wsh[0];
+    }
+    *down = k;
+    if (equal || n > 64) return 0;
+    uint64_t started = 0;  // bit i: some workgroup starts on entry i
+    for (uint32_t g = 0; g < grid; ++g) {
+      const uint32_t r = pool_start_pos(g, sum);
+      uint32_t e = 0;
+      while (e + 1 < n && prefix[e] <= r) ++e;  // = the number of entries whose inclusive prefix sum is <= r
+      started |= 1ull << e;
+    }
+    if (started == (n == 64 ? ~0ull : (1ull << n) - 1)) return sum;
+  }
+}
+
+}  // namespace npow

@@ -13,6 +13,10 @@ client/README.md:31):
   --gpu-local-work-size N       accepted and ignored (search workgroups are 512 lanes on gfx950)
   --shuffle                     pick a random queued request instead of the oldest
   --max-active N                requests searched at once by the GPU work pool (default 4)
+  --ondemand-weight W           no effect on the work server itself, which takes each request's weight from its
+                                "weight" field: the value (1, 2, 4 or 8; default 1) is only handed on by
+                                dpow_weights() to code that builds a DPoW work handler from these options, which
+                                then puts it on its ``ondemand`` requests (``precache`` stays 1)
 
 Without --gpu every visible GPU is used.
 """
@@ -41,10 +45,20 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--max-active", type=int, default=4, metavar="N",
                     help="Requests searched at once by the GPU work pool (1 = strictly one at a time, "
                          "like the reference; at most 64).")
+    ap.add_argument("--ondemand-weight", "--ondemand_weight", dest="ondemand_weight", type=int, default=1,
+                    choices=W.WEIGHTS, metavar="W",
+                    help="No effect on the work server itself (it takes each request's weight from the request's "
+                         "\"weight\" field). The weight (1, 2, 4 or 8) that a DPoW work handler built from these options "
+                         "(dpow_weights) puts on its on-demand requests; precache ones keep weight 1.")
     ap.add_argument("--base-difficulty", default=W.fmt_u64(W.DEFAULT_BASE),
                     help="Threshold multipliers are quoted against (default fffffff800000000).")
     ap.add_argument("-v", "--verbose", action="store_true")
     return ap.parse_args(argv)
+
+
+def dpow_weights(args: argparse.Namespace) -> dict:
+    """The ``weights`` of a :class:`nanopow.dpow.DpowWorkHandler` for these options (--ondemand-weight)."""
+    return {"ondemand": args.ondemand_weight, "precache": 1}
 
 
 LS_CU_LANES = 2048  # lanes per CU of a search launch (npow_pool_kernel_ls2*: 8 waves of 64 per SIMD)

@@ -30,7 +30,7 @@ NPOW_ERR_INVALID_WORK = -5
 NPOW_ERR_CAPACITY = -6
 NPOW_ERR_INTERNAL = -7
 
-NPOW_ABI_VERSION = 6
+NPOW_ABI_VERSION = 7
 # hash paths of npow_values_path
 NPOW_PATH_SEARCH = 0   # the stream the search and sweep kernels execute (four 512-lane workgroups per CU)
 NPOW_PATH_SEQ = 1      # a second generated stream, scheduled without barriers
@@ -45,7 +45,7 @@ EXPORTED_SYMBOLS = (
     "npow_device_stats_get", "npow_device_stats_reset", "npow_version",
     "npow_submit", "npow_wait", "npow_cancel", "npow_pool_config", "npow_pool_status",
     "npow_set_pool_tuning", "npow_values_path", "npow_wait_info", "npow_device_stats_get_sized",
-    "npow_abi_version", "npow_config_cpu_threads", "npow_wait_result",
+    "npow_abi_version", "npow_config_cpu_threads", "npow_wait_result", "npow_submit_weighted",
 )
 
 
@@ -203,6 +203,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.npow_config_cpu_threads.restype = ctypes.c_int
             lib.npow_wait_result.argtypes = [u64, ctypes.c_int64, pu64, pu64]
             lib.npow_wait_result.restype = ctypes.c_int
+        if hasattr(lib, "npow_submit_weighted"):  # ABI 7
+            lib.npow_submit_weighted.argtypes = [u8p, u64, u64, u64, u64, p, u32, pu64]
+            lib.npow_submit_weighted.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -364,12 +367,22 @@ class Engine:
 
     # -- work pool: asynchronous searches ---------------------------------------------------
     def submit(self, root: bytes, threshold: int, start: int = 0, device_mask: int = 0,
-               max_nonces_per_device: int = 0, cancel: Optional[CancelToken] = None) -> "Ticket":
-        """Queue a first-win search and return at once (npow_submit).  Keep `cancel` alive
-        until the ticket's result has been collected (the Ticket holds a reference)."""
+               max_nonces_per_device: int = 0, cancel: Optional[CancelToken] = None, weight: int = 1) -> "Ticket":
+        """Queue a first-win search and return at once (npow_submit_weighted).  Keep `cancel` alive
+        until the ticket's result has been collected (the Ticket holds a reference).
+        weight (1, 2, 4 or 8): the search's share of each GPU among the live unbounded searches, weight /
+        (sum of weights), and its place among the jobs waiting for admission (heaviest first)."""
         t = ctypes.c_uint64(0)
-        _check(self.lib.npow_submit(_root(root), threshold & M64, start & M64, device_mask, max_nonces_per_device,
-                                    cancel.address if cancel else None, ctypes.byref(t)), self.lib)
+        args = (_root(root), threshold & M64, start & M64, device_mask, max_nonces_per_device,
+                cancel.address if cancel else None)
+        if hasattr(self.lib, "npow_submit_weighted"):
+            if not isinstance(weight, int) or isinstance(weight, bool) or not 0 <= weight <= 0xffffffff:
+                raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "weight must be 1, 2, 4 or 8")
+            _check(self.lib.npow_submit_weighted(*args, weight, ctypes.byref(t)), self.lib)
+        elif weight != 1:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow (ABI below 7) has no job weights")
+        else:
+            _check(self.lib.npow_submit(*args, ctypes.byref(t)), self.lib)
         return Ticket(self, t.value, cancel)
 
     def pool_config(self, max_active: int) -> None:

@@ -18,6 +18,11 @@ for the same hash is ignored; the next request is picked at random from the queu
 (WorkQueue._get); a cancel removes a queued hash, or, for an ongoing one, forgets it (the
 result is then not published) and POSTs ``work_cancel``.  ``concurrency`` > 1 runs that many
 request loops against the work server (the reference runs one).
+
+Extension: ``weights`` maps a work type to the ``"weight"`` (1, 2, 4 or 8) its work_generate
+requests carry -- the work server then serves ``ondemand`` (a user is waiting) ahead of
+``precache`` (speculative).  The field is sent only when it is not 1, so a reference work
+server, which does not know it, is asked exactly as before with the default weights.
 """
 from __future__ import annotations
 
@@ -34,6 +39,7 @@ from typing import Awaitable, Callable, Dict, Optional, Tuple
 log = logging.getLogger("nanopow.dpow")
 
 WORK_TYPES = ("ondemand", "precache")
+DEFAULT_WEIGHTS = {"ondemand": 1, "precache": 1}
 
 
 class MessageError(ValueError):
@@ -114,7 +120,11 @@ class DpowWorkHandler:
     """WorkHandler-equivalent: queue of requests -> work server -> published results."""
 
     def __init__(self, worker: HttpWorker, publish: PublishFn, payout: str, concurrency: int = 1,
-                 rng: Optional[random.Random] = None) -> None:
+                 rng: Optional[random.Random] = None, weights: Optional[Dict[str, int]] = None) -> None:
+        self.weights = dict(DEFAULT_WEIGHTS if weights is None else weights)
+        for t, w in self.weights.items():
+            if w not in (1, 2, 4, 8):
+                raise ValueError(f"weight of work type {t!r} must be 1, 2, 4 or 8, not {w!r}")
         self.worker = worker
         self.publish = publish
         self.payout = payout
@@ -186,8 +196,11 @@ class DpowWorkHandler:
             block_hash, difficulty, work_type = await self._next()
             self.ongoing.add(block_hash)
             try:
-                res = await self.worker.post({"action": "work_generate", "hash": block_hash,
-                                              "difficulty": difficulty})
+                body = {"action": "work_generate", "hash": block_hash, "difficulty": difficulty}
+                weight = self.weights.get(work_type, 1)
+                if weight != 1:
+                    body["weight"] = weight
+                res = await self.worker.post(body)
             except Exception as e:  # noqa: BLE001
                 log.error("Work handler loop error: %s", e)
                 self.ongoing.discard(block_hash)

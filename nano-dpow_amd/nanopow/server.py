@@ -20,7 +20,10 @@ Also served: ``work_validate`` (valid / valid_all / valid_receive / difficulty /
 multiplier, @1680400..1680528), ``status`` (generating / queue_size,
 @1679680) and ``benchmark`` (count -> duration / average / hint, @1679992..1680344).
 
-Requests queue FIFO (``--shuffle``: random pick, nano-work-server.exe @1681064).
+Requests queue FIFO (``--shuffle``: random pick, nano-work-server.exe @1681064);
+a request's optional ``"weight"`` (1, 2, 4 or 8 -- this server's extension, the
+reference has no such field) puts it ahead of lighter ones in that queue and gives
+it that share of each GPU among the searches in flight (npow_submit_weighted).
 The reference serves one request at a time; here up to ``max_active`` queued
 requests are handed to libnanopow's work pool at once (npow_submit), where
 every selected GPU searches all of them in the same kernel launches, so a
@@ -61,17 +64,19 @@ class SearchEngine(Protocol):
 
     def submit(self, root: bytes, threshold: int, start: int = 0, device_mask: int = 0,
                max_nonces_per_device: int = 0, cancel: Optional[CancelToken] = None) -> SearchTicket: ...
+    # (an engine that serves weighted requests also takes `weight: int = 1`; passed only when it is not 1)
 
     def work_value(self, root: bytes, nonce: int) -> int: ...
 
 
 class Job:
     __slots__ = ("root", "threshold", "cancel", "done", "reply", "active", "t_queued", "waiters", "t_started",
-                 "ticket", "dispatched", "collector")
+                 "ticket", "dispatched", "collector", "weight")
 
-    def __init__(self, root: bytes, threshold: int) -> None:
+    def __init__(self, root: bytes, threshold: int, weight: int = 1) -> None:
         self.root = root
         self.threshold = threshold
+        self.weight = weight
         self.cancel = CancelToken()
         self.done = threading.Event()
         self.reply: Dict[str, Any] = {}
@@ -192,7 +197,8 @@ class WorkServer:
     def work_generate(self, req: Dict[str, Any]) -> Dict[str, Any]:
         root = W.parse_hash(req)
         threshold = W.requested_threshold(req, self.base)
-        return self._result(self._enqueue(root, threshold))
+        weight = W.parse_weight(req)
+        return self._result(self._enqueue(root, threshold, weight))
 
     def work_cancel(self, req: Dict[str, Any]) -> Dict[str, Any]:
         root = W.parse_hash(req)
@@ -245,7 +251,7 @@ class WorkServer:
                 "hint": "Times in milliseconds"}
 
     # -- queue -------------------------------------------------------------------------
-    def _enqueue(self, root: bytes, threshold: int) -> Job:
+    def _enqueue(self, root: bytes, threshold: int, weight: int = 1) -> Job:
         with self._lock:
             if not self._running:
                 j = Job(root, threshold)
@@ -255,19 +261,25 @@ class WorkServer:
             for j in self._inflight + self._queue:
                 if j.root == root and j.threshold == threshold and not j.cancel.is_set:
                     j.waiters += 1
+                    # a heavier duplicate raises a job that still waits here (its place in the queue and the
+                    # weight it is submitted with); one already in the engine keeps the weight it started with
+                    if not j.active and weight > j.weight:
+                        j.weight = weight
                     return j
-            job = Job(root, threshold)
+            job = Job(root, threshold, weight)
             self._queue.append(job)
             ready = self._pump_locked()
         self._submit(ready)
         return job
 
     def _pump_locked(self) -> List[Job]:
-        """Move queued jobs in flight while fewer than max_active are (FIFO, or a random one
-        with --shuffle); the caller submits them once the lock is released."""
+        """Move queued jobs in flight while fewer than max_active are (the heaviest first; within a
+        weight FIFO, or a random one with --shuffle); the caller submits them once the lock is released."""
         ready = []
         while self._running and self._queue and len(self._inflight) < self.max_active:
-            idx = self.rng.randrange(len(self._queue)) if self.shuffle else 0
+            top = max(j.weight for j in self._queue)
+            heaviest = [i for i, j in enumerate(self._queue) if j.weight == top]
+            idx = self.rng.choice(heaviest) if self.shuffle else heaviest[0]
             job = self._queue.pop(idx)
             job.active = True
             job.t_started = time.perf_counter()
@@ -278,8 +290,10 @@ class WorkServer:
     def _submit(self, jobs: List[Job]) -> None:
         for job in jobs:
             try:
+                # (the keyword only for a weighted request: engines without it keep serving the others)
+                extra = {"weight": job.weight} if job.weight != 1 else {}
                 job.ticket = self.engine.submit(job.root, job.threshold, start=self.rng.getrandbits(64),
-                                                device_mask=self.device_mask, cancel=job.cancel)
+                                                device_mask=self.device_mask, cancel=job.cancel, **extra)
             except Exception as e:  # never leave a client waiting
                 log.error("Error computing work: %s", e)
                 self._complete(job, dict(GENERATION_FAILED))

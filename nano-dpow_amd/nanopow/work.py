@@ -116,6 +116,28 @@ def requested_threshold(req: Dict[str, Any], base: int) -> int:
     return base
 
 
+WEIGHTS = (1, 2, 4, 8)
+
+
+def parse_weight(req: Dict[str, Any]) -> int:
+    """The optional ``"weight"`` of a work_generate request (an integer or a decimal string; this server's
+    extension -- the reference has no such field): the request's share of each GPU among the searches in
+    flight, 1 when absent."""
+    w = req.get("weight")
+    if w is None:
+        return 1
+    bad = RequestError("Bad weight", "Expecting 1, 2, 4 or 8")
+    if isinstance(w, bool) or not isinstance(w, (int, str)):
+        raise bad
+    if isinstance(w, str):
+        if not (w.isascii() and w.isdigit()):
+            raise bad
+        w = int(w)
+    if w not in WEIGHTS:
+        raise bad
+    return w
+
+
 def fmt_u64(x: int) -> str:
     return f"{x & M64:016x}"
 

@@ -73,7 +73,9 @@ static void tickets(int tid, int n) {
     volatile uint32_t cancel = 0;
     uint64_t ticket = 0;
     const uint64_t thr = (i % 3 == 0) ? 0xffffffffffff0000ull : 0xfffffe0000000000ull;
-    int rc = npow_submit(root, thr, 0, g_mask, 0, &cancel, &ticket);
+    // every other ticket weighted (1, 2, 4, 8 in turn): the sorted admission queue and the weighted tables
+    int rc = (i & 1) ? npow_submit_weighted(root, thr, 0, g_mask, 0, &cancel, 1u << ((i >> 1) & 3), &ticket)
+                     : npow_submit(root, thr, 0, g_mask, 0, &cancel, &ticket);
     CHECK(rc == NPOW_OK, "submit rc %d", rc);
     uint64_t nonce = 0, value = 0, done = 0;
     rc = npow_wait(ticket, 2000, &nonce, &value, &done);
