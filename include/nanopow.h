@@ -67,7 +67,9 @@ extern "C" {
  * the ones whose count never came -- a protocol check: 0), linger_ms (the device's lingering launches waiting with
  * nothing to hash, inside kernel_ms) and linger_relays (kills relayed by a lingering workgroup).
  * 7: npow_submit_weighted (a job's weight: its share of each GPU among the live searches, and its place in the
- * admission queue); npow_submit is the same call with weight 1. */
+ * admission queue); npow_submit is the same call with weight 1.
+ * Added within revision 7 (the number stays; callers probe for the symbol): npow_promote (raise the weight of a
+ * search that is waiting or running), and npow_device_stats gains promotions (still written up to the caller's size). */
 #define NPOW_ABI_VERSION 7
 
 /* Hash paths of npow_values_path. */
@@ -133,6 +135,9 @@ typedef struct npow_device_stats {
   uint64_t stale_missing;   /* ... or never, though every launch that held the job ended: a protocol hole, 0 */
   double stale_gpu_delay_us; /* the latest such late count's publish after the job's deciding win, on the GPU's clock
                                 (s_memrealtime; one clock over CU partitions of one GPU, not across GPUs) */
+  /* ---- ABI 7, with npow_promote ---- */
+  uint64_t promotions;      /* promotions (npow_promote) this device published into a running launch: the launch
+                               rebalanced its workgroups to the new weight without ending */
 } npow_device_stats;
 
 /* Outcome of one search (npow_wait_info).  Times are host steady-clock microseconds since
@@ -267,6 +272,16 @@ int npow_wait_result(uint64_t ticket, int64_t timeout_us, uint64_t* nonce_out, u
 
 /* Cancel a ticket (same effect as raising its cancel word). */
 int npow_cancel(uint64_t ticket);
+
+/* Raise the weight of a search that is waiting, admitted or running (added within ABI 7; probe for the symbol):
+ * the job's weight becomes max(current, weight), weight in {1, 2, 4, 8}.  A waiting job moves up the admission queue
+ * (heaviest first, first come first served within a weight).  A job inside a running launch of several searches gets
+ * its new share within that launch -- the launch's workgroups rebalance, nothing ends or restarts (npow_device_stats
+ * promotions counts these) -- and every later launch carries the weight; on each device of a split job, the CPU
+ * workers ignoring it.  NPOW_OK and no change for a weight at or below the current one, and for a search already
+ * decided or cancelled but not yet collected.  NPOW_ERR_BAD_ARGUMENT for any other weight, an unknown or collected
+ * ticket, and a weight above 1 on a bounded search.  Never waits for a GPU.  A weight is never lowered. */
+int npow_promote(uint64_t ticket, uint32_t weight);
 
 /* Jobs searched at once (1..64).  Fewer gives the oldest requests every GPU sooner
  * (lower time-to-work under load); more keeps waves busy when jobs end mid-launch. */

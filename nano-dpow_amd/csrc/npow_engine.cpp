@@ -597,6 +597,7 @@ static int stats_fill(int device, npow_device_stats* out) {
   out->stale_missing = d.stale_missing;
   out->stale_gpu_delay_us = d.stale_gpu_delay_us;
   out->linger_ms = d.linger_ms;
+  out->promotions = d.promotions;
   return NPOW_OK;
 }
 
@@ -625,7 +626,7 @@ int npow_device_stats_reset(int device) try {
   const double cpu = worker_cpu_ms(d);
   std::lock_guard<std::mutex> g(d.stats_mu);
   d.launches = d.nonces = d.invalid = d.early = d.early_mismatch = d.yields = d.dyn = d.kills_relayed = d.late = 0;
-  d.idle_gaps = d.watcher_decisions = d.stale_drains = d.linger_relays = d.stale_late = d.stale_missing = 0;
+  d.promotions = d.idle_gaps = d.watcher_decisions = d.stale_drains = d.linger_relays = d.stale_late = d.stale_missing = 0;
   d.idle_ms = d.linger_ms = d.stale_gpu_delay_us = 0.0;
   d.kernel_ms = 0.0;
   d.clk_ticks = d.clk_ref_ticks = 0.0;
@@ -736,6 +737,13 @@ int npow_wait_result(uint64_t ticket, int64_t timeout_us, uint64_t* nonce_out, u
 int npow_cancel(uint64_t ticket) try {
   if (int rc = check_init()) return rc;
   return pool_cancel(ticket);
+} catch (...) { return guard_exception(); }
+
+int npow_promote(uint64_t ticket, uint32_t weight) try {
+  if (int rc = check_init()) return rc;
+  if (weight != 1 && weight != 2 && weight != 4 && weight != 8)
+    return fail(NPOW_ERR_BAD_ARGUMENT, "weight must be 1, 2, 4 or 8");
+  return pool_promote(ticket, weight);
 } catch (...) { return guard_exception(); }
 
 int npow_pool_config(uint32_t max_active) try {

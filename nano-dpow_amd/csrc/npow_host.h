@@ -65,6 +65,8 @@ struct Device {
   uint64_t early = 0, early_mismatch = 0;  // jobs finished from a published final count (npow_pool.cpp)
   uint64_t yields = 0, dyn = 0;            // launches yielded / jobs that joined a running launch
   uint64_t linger_ends = 0;                // lingering launches ended early (Worker::end_linger)
+  uint64_t promotions = 0;                 // promotions published into a running counted launch (pool_promote)
+  std::atomic<int> counted_inflight{0};    // counted launches in flight (published by the pool worker for pool_promote)
   uint64_t kills_relayed = 0;              // losing jobs stopped by another device's decision (npow_pool.cpp)
   uint64_t late = 0;                       // device-side overshoot: nonces hashed after the job was known over
   uint64_t watcher_decisions = 0;          // jobs the win watcher decided from this device's win records
@@ -203,6 +205,7 @@ int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* va
               npow_search_info* info = nullptr);
 int pool_wait_result(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* value);
 int pool_cancel(uint64_t ticket);
+int pool_promote(uint64_t ticket, uint32_t weight);  // weight: 1, 2, 4 or 8 (npow_promote; checked by the caller)
 int pool_set_max_active(uint32_t n);
 void pool_counts(uint32_t* queued, uint32_t* active);
 

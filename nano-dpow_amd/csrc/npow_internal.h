@@ -148,7 +148,14 @@ struct PoolTable {
                           // weighted shares.  The host halves a crowded table's weights until a workgroup starts
                           // on every entry (pool_table_weights, npow_weights.h).  0: g % n (every weight equal, or a table with
                           // a bounded entry, whose dense mapping needs g % n == e)
-  uint32_t pad[3];
+  uint32_t promo_base;    // the high half of PoolMailbox::kills (the promotion counter, npow_promote) when the table's
+                          // weights were read: a polling wave of a counted launch that reads another value relays
+                          // the boost words of the launch's live entries (ls2_promo_relay), and from then on the
+                          // launch compares counts with the entries' effective shifts (pool_eff_wsh) and balances
+                          // toward every live unbounded entry, not only the dynamic ones
+  uint32_t wdown;         // how many times the table's weights were halved (pool_table_weights): a promoted weight,
+                          // published raw, is halved alike
+  uint32_t pad;
   PoolEntry e[kMaxSlots];
 };
 inline size_t pool_table_bytes(uint32_t n) { return offsetof(PoolTable, e) + (size_t)n * sizeof(PoolEntry); }
@@ -209,6 +216,12 @@ struct PoolDevState {
   // lingering workgroups to read from device memory: one uncached host read per 64 lingering workgroups' looks
   // instead of one each.  Monotonic like ctl; a value older than a launch's table reads as no news (ls2_mirror_ok).
   alignas(64) unsigned long long ctl_mirror[8];
+  // Promotion (npow_promote).  promo_done, per launch ring like kills_done: (the launch's seq << 32) | the promotion
+  // counter up to which a wave of that launch has copied its live entries' pinned boost words into `boost` -- one
+  // scan per promotion and launch; a pick (ls2_choose) reads it to learn whether its launch has seen a promotion.
+  // boost[slot]: pool_boost_mirror of the slot's latest relayed word, raised with an atomic max (npow_weights.h).
+  alignas(64) unsigned long long promo_done[kPoolRing][8];
+  alignas(64) unsigned long long boost[kMaxSlots];
 };
 
 // Pinned host-coherent mailbox of the pool: one win record per slot (the winner stores
@@ -264,12 +277,16 @@ struct PoolMailbox {
   PoolFin fin[kMaxSlots];
   PoolDynEntry dyn[kDynRing];
   uint64_t kill[kMaxSlots];  // kill[s] = gen: the job in slot s (that generation) must stop
+  uint64_t boost[kMaxSlots];  // boost[s] = pool_boost_word(gen, wsh): the job in slot s (that generation) was promoted
+                              // to the weight of that shift (npow_promote; written before the counter below is bumped)
   // High half: bumped by the host when new jobs wait for the next launch (a yield); low half: the
   // dynamic entries published (ring positions, see PoolDynEntry).  One word, so a poll reads both
   // with one uncached read.
   alignas(64) uint64_t ctl;
   // Bumped by the host after it raises any kill word of this device (round 4): a poll lands on one entry,
   // and with n live entries a kill of another entry would wait ~n polls for a wave on that entry.
+  // That is its low half (PoolTable::kill_base).  The high half counts promotions (npow_promote, PoolTable::promo_base):
+  // the polls of counted launches of several entries read this word anyway, so one uncached read brings both.
   alignas(64) uint64_t kills;
   alignas(64) PoolClk clk[kPoolRing][kClkWaves];  // [launch ring][XCD] (host: kEventRing == kPoolRing)
 #ifdef NPOW_DIAG_TIMES

@@ -626,6 +626,47 @@ __device__ __forceinline__ unsigned long long ls2_wgs(PoolDevState* st, uint32_t
   return __hip_atomic_load(&st->count[slot][ls2_shard()].wgs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Promotion (npow_promote, npow_weights.h).  The host raised the weight of a job this launch may hold: it wrote the
+// slot's pinned boost word and then bumped the promotion counter, the high half of PoolMailbox::kills, which the
+// polls of counted launches of several entries read anyway.  Like a kill it is relayed once per launch and counter
+// value (PoolDevState::promo_done, keyed by (seq, counter) as kills_done is): the one poller that first sees the new
+// value reads the boost word of each live entry (uncached, after the counter: the host wrote them before its release)
+// and raises the slot's mirror in device memory, which every later comparison of two entries' workgroup counts in
+// this launch reads instead of the pinned words (ls2_wsh_eff).  A launch whose counter still equals its table's
+// promo_base reads none of this.  Lane 0 of a polling or lingering wave.
+__device__ __forceinline__ void ls2_promo_relay(const PoolTable* tab, PoolDevState* st, PoolMailbox* mb, uint32_t nd,
+                                                uint32_t promo) {
+  unsigned long long* const pd = &st->promo_done[tab->ring & (kPoolRing - 1)][0];
+  const unsigned long long key = ((unsigned long long)tab->seq << 32) | promo;
+  if (__hip_atomic_load(pd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == key) return;
+  __atomic_signal_fence(__ATOMIC_SEQ_CST);  // the boost words after the counter (as ls2_poll's kill words)
+  const unsigned long long over = __hip_atomic_load(&s_over, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  for (uint32_t k = 0; k < tab->n + nd; ++k) {
+    if ((over >> k) & 1) continue;
+    const EntryHdr q = ls2_hdr(tab, mb, k);
+    if (q.bounded || load_dead(st, q.slot) >= q.gen) continue;
+    const uint64_t word = __hip_atomic_load(&mb->boost[q.slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (pool_boost_gen(word) == q.gen)
+      __hip_atomic_fetch_max(&st->boost[q.slot], (unsigned long long)pool_boost_mirror(word), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // (a max: of two relays racing for different counter values the later key stands, whichever stores last -- and
+  // the mirrors, raised by max too, hold the newest words either of them read)
+  __hip_atomic_fetch_max(pd, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// Has this launch relayed a promotion (its promo_done holds its own seq and a counter other than its table's)?
+__device__ __forceinline__ bool ls2_promoted(const PoolTable* tab, PoolDevState* st) {
+  const unsigned long long pd =
+      __hip_atomic_load(&st->promo_done[tab->ring & (kPoolRing - 1)][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return (uint32_t)(pd >> 32) == tab->seq && (uint32_t)pd != tab->promo_base;
+}
+// An entry's shift in a launch that has seen a promotion: the slot's mirror if it is of the entry's generation.
+__device__ __forceinline__ uint32_t ls2_wsh_eff(const PoolTable* tab, PoolDevState* st, uint32_t slot, uint64_t gen,
+                                                uint32_t wsh) {
+  return pool_eff_wsh(__hip_atomic_load(&st->boost[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), gen, wsh,
+                      tab->wdown);
+}
+
 // A polling wave (lane 0 only): the host words of the entry.  Returns bit 0 set when the wave's
 // workgroup must leave the entry, and bit 1 too when the reason is the pinned kill word: new jobs wait and the entry is unbounded (a yield), it was
 // killed, or it is unbounded and a dynamic entry would, with this workgroup on it, still hold no more workgroups
@@ -647,9 +688,12 @@ __device__ __forceinline__ uint32_t ls2_poll(const PoolTable* tab, PoolDevState*
   // the counter there, whose uncached read at every poll was 0.76 MB per 10-ms launch of PMC traffic)
   // (nor in a launch of one entry so far: a lingering launch is counted from its first entry on)
   const uint32_t nd = ls2_dyn_count(tab, ctl);
-  const uint32_t kills = tab->counted && tab->n + nd > 1
-                             ? (uint32_t)__hip_atomic_load(&mb->kills, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
-                             : tab->kill_base;
+  // (the word's high half is the promotion counter: the same read brings it; the polls that skip the read see none)
+  const uint64_t kw = tab->counted && tab->n + nd > 1
+                          ? __hip_atomic_load(&mb->kills, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
+                          : (((uint64_t)tab->promo_base << 32) | tab->kill_base);
+  const uint32_t kills = (uint32_t)kw;
+  const bool promoted = (uint32_t)(kw >> 32) != tab->promo_base;
   (void)seen;  // (the entries it looks at here are read past the caches: ls2_hdr)
   bool leave = false;
   // A job of this launch was killed since it was built, and no wave has relayed that kill yet: relay every such
@@ -675,6 +719,7 @@ __device__ __forceinline__ uint32_t ls2_poll(const PoolTable* tab, PoolDevState*
     }
     __hip_atomic_store(kd, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+  if (promoted) ls2_promo_relay(tab, st, mb, nd, (uint32_t)(kw >> 32));
   if ((ctl >> 32) != (tab->yield_base >> 32)) {
     // (only the entries still live: each kill is an atomic and, counted, 8 serial loads -- over a lingering launch's
     // ring of 33 mostly finished entries ~0.35 ms, which held up a losing search's stop when the host ended the
@@ -696,11 +741,15 @@ __device__ __forceinline__ uint32_t ls2_poll(const PoolTable* tab, PoolDevState*
     ls2_kill(st, mb, pe->slot, pe->gen, tab->counted != 0);  // relay
     leave = killed = true;
   }
-  if (!leave && !pe->bounded && nd > 0) {
+  // (a launch that has seen a promotion balances toward every live unbounded entry -- a promoted table entry is a
+  // target like a dynamic one -- and compares with the effective shifts, the slots' mirrors: the same rule, so the
+  // no-ping-pong argument above holds as written)
+  if (!leave && !pe->bounded && (nd > 0 || promoted)) {
     const unsigned long long mine = ls2_wgs(st, pe->slot);
     const unsigned long long over = __hip_atomic_load(&s_over, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     unsigned long long found = 0;
-    for (uint32_t k = tab->n; k < tab->n + nd && !leave; ++k) {
+    const uint32_t sm = promoted ? ls2_wsh_eff(tab, st, pe->slot, pe->gen, pe->wsh) : pe->wsh & 3u;
+    for (uint32_t k = promoted ? 0u : tab->n; k < tab->n + nd && !leave; ++k) {
       if (k == e || ((over >> k) & 1)) continue;
       const EntryHdr q = ls2_hdr(tab, mb, k);
       if (q.bounded || load_dead(st, q.slot) >= q.gen) {
@@ -708,8 +757,8 @@ __device__ __forceinline__ uint32_t ls2_poll(const PoolTable* tab, PoolDevState*
         continue;
       }
       // (q + 1) << wsh_q <= (mine - 1) << wsh_mine, without the subtraction; equal weights: q + 2 <= mine
-      const uint32_t sq = q.wsh & 3u, sm = pe->wsh & 3u;
-      leave = ((ls2_wgs(st, q.slot) + 1) << sq) + (1ull << sm) <= (mine << sm);
+      const uint32_t sq = promoted ? ls2_wsh_eff(tab, st, q.slot, q.gen, q.wsh) : q.wsh & 3u;
+      leave = pool_should_move(ls2_wgs(st, q.slot), sq, mine, sm);
     }
     ls2_mark_over(found);
   }
@@ -723,6 +772,7 @@ __device__ __forceinline__ uint32_t ls2_choose(const PoolTable* tab, PoolDevStat
                                                uint32_t nd, uint32_t* seen, uint32_t lane, uint32_t g) {
   const uint32_t N = tab->n + nd;  // <= kMaxSlots = 64: one lane each
   ls2_fresh(tab, st, nd, seen);
+  const bool promoted = ls2_promoted(tab, st);  // (one device-memory word per pick; the mirrors only if so)
   for (int attempt = 0; attempt < 4; ++attempt) {
     unsigned long long key = ~0ull;
     bool over = false;
@@ -731,7 +781,8 @@ __device__ __forceinline__ uint32_t ls2_choose(const PoolTable* tab, PoolDevStat
       ConstEntry* q = ls2_entry(tab, mb, lane);
       if (!q->bounded && load_dead(st, q->slot) < q->gen) {
         const uint32_t tie = ((lane + 1u) * 0x9e3779b1u) ^ (g * 0x85ebca6bu);
-        key = ((ls2_wgs(st, q->slot) << (q->wsh & 3u)) << 32) | (tie & ~63u) | lane;
+        const uint32_t sq = promoted ? ls2_wsh_eff(tab, st, q->slot, q->gen, q->wsh) : q->wsh & 3u;
+        key = ((ls2_wgs(st, q->slot) << sq) << 32) | (tie & ~63u) | lane;
       } else {
         over = true;
       }
@@ -775,7 +826,10 @@ __device__ __forceinline__ uint32_t ls2_choose(const PoolTable* tab, PoolDevStat
 // is joined and hashed again; past the launch's budget its joiners leave within 4 iterations, ending the launch).
 // Lane 0.  (Inlined: the search loop keeps its register allocation, tools/kernel_loop_census.py, and no call frame.)
 __device__ __forceinline__ void ls2_linger_relay(const PoolTable* tab, PoolDevState* st, PoolMailbox* mb, uint32_t nd) {
-  const uint32_t kills = (uint32_t)__hip_atomic_load(&mb->kills, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  const uint64_t kw = __hip_atomic_load(&mb->kills, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  const uint32_t kills = (uint32_t)kw;
+  // promotions too (the word's high half): an entry promoted while its launch lingers is then picked at its new weight
+  if ((uint32_t)(kw >> 32) != tab->promo_base) ls2_promo_relay(tab, st, mb, nd, (uint32_t)(kw >> 32));
   unsigned long long* const kd = &st->kills_done[tab->ring & (kPoolRing - 1)][0];
   const unsigned long long key = ((unsigned long long)tab->seq << 32) | kills;
   if (kills == tab->kill_base || __hip_atomic_load(kd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == key) return;

@@ -712,6 +712,12 @@ class Worker {
     d_.active_slots.store(active, std::memory_order_release);
     d_.worker_busy.store(busy(), std::memory_order_release);
   }
+  // for pool_promote's count of promotions published into a running launch (npow_device_stats.promotions)
+  void publish_counted() {
+    int c = 0;
+    for (const PoolInflight& f : q_) c += f.counted ? 1 : 0;
+    d_.counted_inflight.store(c, std::memory_order_release);
+  }
   void check_slots();
   int launch(bool empty_linger = false);
   int queue_readbacks();
@@ -1181,6 +1187,9 @@ int Worker::launch(bool empty_linger) {
   t.seq = (uint32_t)seq_;
   {
     std::lock_guard<std::mutex> g(g_pool.mu);  // issued[] is shared with other workers' reads
+    // the promotion counter with the jobs' weights, both under the pool lock (pool_promote writes them under it): a
+    // promotion is either in the weights read below or bumps the counter past this base, which the kernel then sees
+    t.promo_base = (uint32_t)(__atomic_load_n(&d_.pmb->kills, __ATOMIC_ACQUIRE) >> 32);
     const double t_issue = now_us();
     for (uint32_t e = 0; e < n; ++e) {
       Slot& sl = slots_[idx[e]];
@@ -1229,6 +1238,8 @@ int Worker::launch(bool empty_linger) {
     t.wsum = pool_table_weights(weights, n, (uint32_t)sh.grid, wshs, &wdown);
     for (uint32_t e = 0; e < n; ++e) t.e[e].wsh = wshs[e];
   }
+  t.wdown = wdown;  // (a promoted weight is published raw: the kernel halves it as the table's were, pool_promoted_wsh)
+  t.pad = 0;
   if (lingers(d_) && !bounded && g_budget_us.load() > 0) {
     // each lingering workgroup reads the pinned ctl word once in P looks (phase g): ~2 reads per look grid-wide
     uint32_t P = 1;
@@ -1264,6 +1275,7 @@ int Worker::launch(bool empty_linger) {
   for (uint32_t e = 0; e < n; ++e) NPOW_DBG(" %d/g%llu", idx[e], (unsigned long long)t.e[e].gen);
   NPOW_DBG("\n");
   q_.push_back({seq_, r, (uint32_t)ctl_, t.yield_base, t.counted != 0, t.linger != 0, wdown});
+  publish_counted();
   return NPOW_OK;
 }
 
@@ -1377,6 +1389,7 @@ int Worker::retire() {
     NPOW_DBGT("nanopow[%d]: launch %llu done\n", d_.id, (unsigned long long)q_.front().seq);
     retired_seq_ = q_.front().seq;
     q_.pop_front();
+    publish_counted();
     front_start_ = std::chrono::steady_clock::now();  // the next one (if any) has just started
   }
   constexpr size_t row = kPoolDoneShards * 8;
@@ -2009,6 +2022,47 @@ int pool_cancel(uint64_t ticket) {
     finish_locked(j);
   } else {
     notify_workers_locked();  // the devices' workers stop its waves at their next step, now rather than after a nap
+  }
+  return NPOW_OK;
+}
+
+// Raise a job's weight (npow_promote; the caller checked the weight).  Only the pool lock, as pool_cancel: nothing
+// here waits for a GPU.  A waiting job moves up the admission queue.  An admitted one carries the new weight into
+// every later table and dynamic entry, and for each GPU that holds it now (a slot and a generation) the slot's pinned
+// boost word is written and the device's promotion counter bumped (release: the word first), so that a running
+// counted launch rebalances to the new weight without ending (npow_kernel.hip ls2_promo_relay).  A launch that does
+// not read the counter -- a one-entry one -- or none at all loses nothing: the next table has the weight.
+int pool_promote(uint64_t ticket, uint32_t weight) {
+  std::lock_guard<std::mutex> g(g_pool.mu);
+  auto it = g_pool.tickets.find(ticket);
+  if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  const JobP& j = it->second;
+  if (weight > 1 && j->max_per_dev)
+    return fail(NPOW_ERR_BAD_ARGUMENT, "a bounded search (max_nonces_per_device) takes weight 1 only");
+  if (j->finished || j->decided || j->cancel_req || weight <= j->weight) return NPOW_OK;
+  j->weight = weight;
+  if (!j->admitted) {
+    // its place in the waiting queue: behind the last job at least as heavy (pool_submit)
+    auto at = std::find(g_pool.waiting.begin(), g_pool.waiting.end(), j);
+    if (at != g_pool.waiting.end()) {
+      JobP keep = *at;
+      at = g_pool.waiting.erase(at);
+      while (at != g_pool.waiting.begin() && (*(at - 1))->weight < weight) --at;
+      g_pool.waiting.insert(at, keep);
+    }
+    return NPOW_OK;
+  }
+  for (size_t k = 0; k < j->devs.size(); ++k) {
+    if (!j->on_dev[k] || j->dev_slot[k] < 0) continue;  // (not adopted yet; the CPU device has no slot)
+    Device& d = *g_devs[(size_t)j->devs[k]];
+    if (d.cpu_threads || !d.pmb) continue;
+    __atomic_store_n(&d.pmb->boost[j->dev_slot[k]], pool_boost_word(j->dev_gen[k], pool_wsh(weight)), __ATOMIC_RELEASE);
+    __atomic_fetch_add(&d.pmb->kills, 1ull << 32, __ATOMIC_RELEASE);  // after the word: the high half (promotions)
+    // counted as published into a running launch: a counted launch is in flight and the job is in one
+    if (d.counted_inflight.load(std::memory_order_acquire) > 0 && j->t_launch_dev[k] != 0) {
+      std::lock_guard<std::mutex> sg(d.stats_mu);
+      d.promotions++;
+    }
   }
   return NPOW_OK;
 }

@@ -26,6 +26,31 @@ NPOW_HD inline uint32_t pool_start_pos(uint32_t g, uint32_t wsum) {
   return (uint32_t)(((uint64_t)(uint32_t)(g * 0x9E3779B9u) * wsum) >> 32);
 }
 
+// Promotion (npow_promote): the host raises the weight of a job some running launch holds by writing the slot's
+// pinned boost word, (gen << 2) | wsh of the job's raw new weight, and then bumping the promotion counter (the high
+// half of PoolMailbox::kills).  One poller of each launch copies the words of its live entries into device memory
+// (PoolDevState::boost) as (gen << 2) | level, level = 3 - wsh = log2(weight): generations and, within one, weights
+// only grow, so the mirror is raised with an atomic max and two relays racing on one slot cannot leave the older
+// word behind.  An entry's effective shift is the mirror's when its generation is the entry's own, on the launch's
+// scale (its table's weights were halved `wdown` times, PoolTable::wdown: floor at weight 1 = shift 3, which is
+// what pool_table_weights and Worker::dyn_add give a job of that weight); otherwise the entry's own wsh.
+NPOW_HD inline uint64_t pool_boost_word(uint64_t gen, uint32_t wsh) { return (gen << 2) | (wsh & 3u); }
+NPOW_HD inline uint64_t pool_boost_gen(uint64_t word) { return word >> 2; }
+NPOW_HD inline uint32_t pool_boost_wsh(uint64_t word) { return (uint32_t)word & 3u; }
+NPOW_HD inline uint64_t pool_boost_mirror(uint64_t word) { return (word & ~3ull) | (3u - ((uint32_t)word & 3u)); }
+NPOW_HD inline uint32_t pool_promoted_wsh(uint32_t wsh, uint32_t wdown) {  // min(3, wsh + wdown)
+  const uint32_t s = (wsh & 3u) + wdown;
+  return s < 3u ? s : 3u;
+}
+NPOW_HD inline uint32_t pool_eff_wsh(uint64_t mirror, uint64_t gen, uint32_t own_wsh, uint32_t wdown) {
+  return (mirror >> 2) == gen ? pool_promoted_wsh(3u - ((uint32_t)mirror & 3u), wdown) : (own_wsh & 3u);
+}
+// The balancing rule of ls2_poll: a workgroup of an entry with `mine` workgroups (shift sm) moves to one with `q`
+// (shift sq) when, with it there, that entry still holds no more for its weight than this one without it.
+NPOW_HD inline bool pool_should_move(unsigned long long q, uint32_t sq, unsigned long long mine, uint32_t sm) {
+  return ((q + 1) << sq) + (1ull << sm) <= (mine << sm);
+}
+
 // The weights a launch of `grid` workgroups gives its n unbounded table entries, from the jobs' weights w[0..n)
 // (each 1, 2, 4 or 8): wsh[i] = PoolEntry::wsh of entry i; *down = how many times every weight was halved (the
 // launch's dynamic entries are halved alike, Worker::dyn_add); returns PoolTable::wsum, the start map's modulus,

@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "npow_submit", "npow_wait", "npow_cancel", "npow_pool_config", "npow_pool_status",
     "npow_set_pool_tuning", "npow_values_path", "npow_wait_info", "npow_device_stats_get_sized",
     "npow_abi_version", "npow_config_cpu_threads", "npow_wait_result", "npow_submit_weighted",
+    "npow_promote",
 )
 
 
@@ -89,6 +90,7 @@ class DeviceStats(ctypes.Structure):
         ("stale_late", ctypes.c_uint64),
         ("stale_missing", ctypes.c_uint64),
         ("stale_gpu_delay_us", ctypes.c_double),
+        ("promotions", ctypes.c_uint64),     # ABI 7, with npow_promote
     ]
 
 
@@ -206,6 +208,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         if hasattr(lib, "npow_submit_weighted"):  # ABI 7
             lib.npow_submit_weighted.argtypes = [u8p, u64, u64, u64, u64, p, u32, pu64]
             lib.npow_submit_weighted.restype = ctypes.c_int
+        if hasattr(lib, "npow_promote"):  # added within ABI 7: probed for
+            lib.npow_promote.argtypes = [u64, u32]
+            lib.npow_promote.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -311,6 +316,20 @@ class Ticket:
     def cancel(self) -> None:
         if self.result is None:
             _check(self.engine.lib.npow_cancel(self.ticket), self.engine.lib)
+
+    def promote(self, weight: int) -> None:
+        """Raise the search's weight to max(current, weight), weight in {1, 2, 4, 8} (npow_promote): a waiting
+        search moves up the admission queue, a running one gets its new share inside the launch that holds it.
+        NanoPowError(NPOW_ERR_BAD_ARGUMENT) for another weight, a collected ticket, a bounded search -- and when
+        the loaded library has no npow_promote."""
+        lib = self.engine.lib
+        if not hasattr(lib, "npow_promote"):
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_promote")
+        if not isinstance(weight, int) or isinstance(weight, bool) or not 0 <= weight <= 0xffffffff:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "weight must be 1, 2, 4 or 8")
+        if self.result is not None:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
+        _check(lib.npow_promote(self.ticket, weight), lib)
 
     def __del__(self) -> None:
         # An abandoned ticket: cancel its search and collect it, so the engine forgets the job

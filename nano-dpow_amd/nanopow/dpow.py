@@ -23,6 +23,14 @@ Extension: ``weights`` maps a work type to the ``"weight"`` (1, 2, 4 or 8) its w
 requests carry -- the work server then serves ``ondemand`` (a user is waiting) ahead of
 ``precache`` (speculative).  The field is sent only when it is not 1, so a reference work
 server, which does not know it, is asked exactly as before with the default weights.
+
+Promotion, part of that extension: the hub answers a service request for a hash whose precache
+is pending by publishing ``work/ondemand`` for the same hash (server/dpow_server.py:287-328).
+When the new message's type has a heavier configured weight than the one the hash was taken at,
+and its difficulty is not above it, a queued hash is retyped to the heavier type and an ongoing
+one is raised at the work server (``work_promote``, nanopow.server) -- its running search gets
+the heavier share at once -- and its result is published under the heavier type.  With the
+default weights (all 1) nothing is heavier: the message is ignored as in the reference.
 """
 from __future__ import annotations
 
@@ -116,6 +124,21 @@ class HttpWorker:
 PublishFn = Callable[[str, bytes], Awaitable[None]]
 
 
+class _Ongoing(dict):
+    """The ongoing requests, hash -> [difficulty, work_type] (the type may be raised by a promotion), with
+    the set-like discard() of the reference's ``work_ongoing`` (work_handler.py:39)."""
+
+    def discard(self, block_hash: str) -> None:
+        self.pop(block_hash, None)
+
+
+def _difficulty_not_above(new: str, old: str) -> bool:
+    try:
+        return int(new, 16) <= int(old, 16)
+    except ValueError:
+        return False
+
+
 class DpowWorkHandler:
     """WorkHandler-equivalent: queue of requests -> work server -> published results."""
 
@@ -131,10 +154,10 @@ class DpowWorkHandler:
         self.concurrency = concurrency
         self.rng = rng or random.Random()
         self.queue: Dict[str, Tuple[str, str]] = {}   # hash -> (difficulty, work_type)
-        self.ongoing: set = set()
+        self.ongoing: _Ongoing = _Ongoing()
         self._ready = asyncio.Event()
         self._tasks = []
-        self.stats = {"queued": 0, "ignored": 0, "sent": 0, "cancelled": 0, "errors": 0}
+        self.stats = {"queued": 0, "ignored": 0, "sent": 0, "cancelled": 0, "errors": 0, "promoted": 0}
 
     async def start(self) -> None:
         # WorkHandler.start: the probe must answer with an "error" field (work_handler.py:53)
@@ -165,7 +188,22 @@ class DpowWorkHandler:
 
     async def queue_work(self, work_type: str, block_hash: str, difficulty: str) -> None:
         if block_hash in self.queue or block_hash in self.ongoing:
-            self.stats["ignored"] += 1
+            # the same hash again under a heavier type (module docstring): promote it; else ignored as in the reference
+            queued = block_hash in self.queue
+            old_difficulty, old_type = self.queue[block_hash] if queued else self.ongoing[block_hash]
+            weight = self.weights.get(work_type, 1)
+            if weight <= self.weights.get(old_type, 1) or not _difficulty_not_above(difficulty, old_difficulty):
+                self.stats["ignored"] += 1
+                return
+            self.stats["promoted"] += 1
+            if queued:
+                self.queue[block_hash] = (old_difficulty, work_type)
+                return
+            self.ongoing[block_hash][1] = work_type  # its result is published under the heavier type
+            try:
+                await self.worker.post({"action": "work_promote", "hash": block_hash, "weight": weight})
+            except Exception as e:  # noqa: BLE001 -- the search goes on at its old weight
+                log.error("Work handler promote error: %s", e)
             return
         self.queue[block_hash] = (difficulty, work_type)
         self.stats["queued"] += 1
@@ -194,7 +232,7 @@ class DpowWorkHandler:
     async def _loop(self) -> None:
         while True:
             block_hash, difficulty, work_type = await self._next()
-            self.ongoing.add(block_hash)
+            self.ongoing[block_hash] = [difficulty, work_type]
             try:
                 body = {"action": "work_generate", "hash": block_hash, "difficulty": difficulty}
                 weight = self.weights.get(work_type, 1)
@@ -208,7 +246,7 @@ class DpowWorkHandler:
                 continue
             if block_hash not in self.ongoing:  # cancelled meanwhile
                 continue
-            self.ongoing.discard(block_hash)
+            work_type = self.ongoing.pop(block_hash)[1]  # (a promotion may have raised it)
             if "work" in res:
                 await self.publish(*result_message(work_type, block_hash, res["work"], self.payout))
                 self.stats["sent"] += 1

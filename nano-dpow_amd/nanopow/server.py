@@ -24,6 +24,11 @@ Requests queue FIFO (``--shuffle``: random pick, nano-work-server.exe @1681064);
 a request's optional ``"weight"`` (1, 2, 4 or 8 -- this server's extension, the
 reference has no such field) puts it ahead of lighter ones in that queue and gives
 it that share of each GPU among the searches in flight (npow_submit_weighted).
+A duplicate request with a heavier weight raises the job it joins, also when its
+search is already running (npow_promote: the share changes inside the running
+launch), and ``{"action": "work_promote", "hash": ..., "weight": ...}`` -- this
+server's extension too, answered ``{}`` like ``work_cancel`` whether or not a job
+matched -- raises every queued or running job of that hash.  Weights only rise.
 The reference serves one request at a time; here up to ``max_active`` queued
 requests are handed to libnanopow's work pool at once (npow_submit), where
 every selected GPU searches all of them in the same kernel launches, so a
@@ -184,6 +189,8 @@ class WorkServer:
                 return self.work_generate(req)
             if action == "work_cancel":
                 return self.work_cancel(req)
+            if action == "work_promote":
+                return self.work_promote(req)
             if action == "work_validate":
                 return self.work_validate(req)
             if action == "status":
@@ -215,6 +222,36 @@ class WorkServer:
             j.resolve({"error": "Cancelled"})
         log.info("Cancel %s", root.hex().upper())
         return {}
+
+    def work_promote(self, req: Dict[str, Any]) -> Dict[str, Any]:
+        """Raise every queued or in-flight job of the hash to the weight (this server's extension)."""
+        root = W.parse_hash(req)
+        weight = W.parse_weight(req)
+        with self._lock:
+            raised = [j for j in self._inflight + self._queue
+                      if j.root == root and not j.cancel.is_set and self._raise_locked(j, weight)]
+        for j in raised:
+            self._promote(j, weight)
+        log.info("Promote %s to weight %d (%d jobs)", root.hex().upper(), weight, len(raised))
+        return {}
+
+    def _raise_locked(self, job: Job, weight: int) -> bool:
+        """Raise the job's weight; True when its search is in the engine and must be promoted there (_promote,
+        once the lock is released).  A job still waiting here is submitted with the weight, and so is one whose
+        submit is under way: _submit compares the weight again once the ticket exists."""
+        if weight <= job.weight:
+            return False
+        job.weight = weight
+        return job.active and job.ticket is not None
+
+    def _promote(self, job: Job, weight: int) -> None:
+        t = job.ticket
+        if t is None or not hasattr(t, "promote"):  # an engine without promotion keeps serving
+            return
+        try:
+            t.promote(weight)
+        except Exception as e:  # (its search ended and was collected meanwhile: nothing to raise)
+            log.debug("promote %s: %s", job.root.hex().upper(), e)
 
     def work_validate(self, req: Dict[str, Any]) -> Dict[str, Any]:
         root = W.parse_hash(req)
@@ -262,13 +299,18 @@ class WorkServer:
                 if j.root == root and j.threshold == threshold and not j.cancel.is_set:
                     j.waiters += 1
                     # a heavier duplicate raises a job that still waits here (its place in the queue and the
-                    # weight it is submitted with); one already in the engine keeps the weight it started with
-                    if not j.active and weight > j.weight:
-                        j.weight = weight
-                    return j
-            job = Job(root, threshold, weight)
-            self._queue.append(job)
-            ready = self._pump_locked()
+                    # weight it is submitted with), and promotes one already in the engine (npow_promote)
+                    dup, promote = j, self._raise_locked(j, weight)
+                    break
+            else:
+                dup, promote = None, False
+                job = Job(root, threshold, weight)
+                self._queue.append(job)
+                ready = self._pump_locked()
+        if dup is not None:
+            if promote:
+                self._promote(dup, weight)
+            return dup
         self._submit(ready)
         return job
 
@@ -291,9 +333,15 @@ class WorkServer:
         for job in jobs:
             try:
                 # (the keyword only for a weighted request: engines without it keep serving the others)
-                extra = {"weight": job.weight} if job.weight != 1 else {}
-                job.ticket = self.engine.submit(job.root, job.threshold, start=self.rng.getrandbits(64),
-                                                device_mask=self.device_mask, cancel=job.cancel, **extra)
+                sent = job.weight
+                extra = {"weight": sent} if sent != 1 else {}
+                ticket = self.engine.submit(job.root, job.threshold, start=self.rng.getrandbits(64),
+                                            device_mask=self.device_mask, cancel=job.cancel, **extra)
+                with self._lock:  # (a heavier duplicate may have come while the submit was under way)
+                    job.ticket = ticket
+                    now = job.weight
+                if now > sent:
+                    self._promote(job, now)
             except Exception as e:  # never leave a client waiting
                 log.error("Error computing work: %s", e)
                 self._complete(job, dict(GENERATION_FAILED))

@@ -120,7 +120,7 @@ WEIGHTS = (1, 2, 4, 8)
 
 
 def parse_weight(req: Dict[str, Any]) -> int:
-    """The optional ``"weight"`` of a work_generate request (an integer or a decimal string; this server's
+    """The optional ``"weight"`` of a work_generate or work_promote request (an integer or a decimal string; this server's
     extension -- the reference has no such field): the request's share of each GPU among the searches in
     flight, 1 when absent."""
     w = req.get("weight")

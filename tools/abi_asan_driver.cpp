@@ -77,6 +77,11 @@ static void tickets(int tid, int n) {
     int rc = (i & 1) ? npow_submit_weighted(root, thr, 0, g_mask, 0, &cancel, 1u << ((i >> 1) & 3), &ticket)
                      : npow_submit(root, thr, 0, g_mask, 0, &cancel, &ticket);
     CHECK(rc == NPOW_OK, "submit rc %d", rc);
+    // every third ticket promoted while it waits or runs (npow_promote: the queue's re-ordering, the pinned words)
+    if (i % 3 == 1) {
+      rc = npow_promote(ticket, 8);
+      CHECK(rc == NPOW_OK, "promote rc %d", rc);
+    }
     uint64_t nonce = 0, value = 0, done = 0;
     rc = npow_wait(ticket, 2000, &nonce, &value, &done);
     if (rc == NPOW_PENDING) {
