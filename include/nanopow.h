@@ -42,6 +42,7 @@ extern "C" {
 #define NPOW_CANCELLED 1
 #define NPOW_EXHAUSTED 2
 #define NPOW_PENDING 3             /* npow_wait: timeout elapsed, the ticket is still valid */
+#define NPOW_TOO_LATE 4   /* npow_retarget: the search was already decided or cancelled (not yet collected); unchanged */
 #define NPOW_ERR_NOT_INITIALISED (-1)
 #define NPOW_ERR_NO_DEVICE (-2)
 #define NPOW_ERR_BAD_ARGUMENT (-3)
@@ -69,7 +70,9 @@ extern "C" {
  * 7: npow_submit_weighted (a job's weight: its share of each GPU among the live searches, and its place in the
  * admission queue); npow_submit is the same call with weight 1.
  * Added within revision 7 (the number stays; callers probe for the symbol): npow_promote (raise the weight of a
- * search that is waiting or running), and npow_device_stats gains promotions (still written up to the caller's size). */
+ * search that is waiting or running), and npow_device_stats gains promotions (still written up to the caller's size);
+ * npow_retarget (raise the threshold of a search that is waiting or running; NPOW_TOO_LATE), and npow_search_info
+ * gains retargets / stale_hits / stale_wins (likewise written up to the caller's size). */
 #define NPOW_ABI_VERSION 7
 
 /* Hash paths of npow_values_path. */
@@ -169,6 +172,12 @@ typedef struct npow_search_info {
   double launch_all_us;     /* every device of the job had issued a launch holding it */
   double win_seen_us;       /* the deciding device's winner record was read by the host (decide_us follows its CPU
                                re-validation) */
+  /* ---- ABI 7, with npow_retarget ---- */
+  uint64_t retargets;       /* raises of the search's threshold that took effect */
+  uint64_t stale_hits;      /* lanes whose value met an older threshold but not the current one, refused on the GPU:
+                               the search went on in place */
+  uint64_t stale_wins;      /* wins a device published under an older threshold: the host refused them and re-armed
+                               the search on that device (the fallback; not invalid work) */
 } npow_search_info;
 
 /* CPU workers (nano-work-server.exe @1681064 `--cpu-threads N`): before npow_init, ask it to add
@@ -282,6 +291,16 @@ int npow_cancel(uint64_t ticket);
  * decided or cancelled but not yet collected.  NPOW_ERR_BAD_ARGUMENT for any other weight, an unknown or collected
  * ticket, and a weight above 1 on a bounded search.  Never waits for a GPU.  A weight is never lowered. */
 int npow_promote(uint64_t ticket, uint32_t weight);
+
+/* Raise the threshold of a search that is waiting, admitted or running (added within ABI 7; probe for the symbol):
+ * the job's threshold becomes max(current, threshold) -- it is never lowered, and a threshold at or below the current
+ * one is NPOW_OK with no effect.  Nothing ends or restarts: the search keeps its slot, its weight and its place in the
+ * nonce space on every device of a split job, the GPUs pass over hits that no longer qualify (npow_search_info
+ * stale_hits) and the CPU workers compare with the current threshold.  After NPOW_OK every result the ticket returns
+ * has value >= threshold.  NPOW_TOO_LATE when the search was already decided, cancelled or finished (not yet
+ * collected): its result stands and may be below `threshold`.  NPOW_ERR_BAD_ARGUMENT for an unknown or collected
+ * ticket.  Bounded searches are accepted: the threshold does not touch their coverage.  Never waits for a GPU. */
+int npow_retarget(uint64_t ticket, uint64_t threshold);
 
 /* Jobs searched at once (1..64).  Fewer gives the oldest requests every GPU sooner
  * (lower time-to-work under load); more keeps waves busy when jobs end mid-launch. */

@@ -91,7 +91,7 @@ void hash_job(CpuShared& sh, Device& d, const JobP& jp, size_t k) {
       for (; n < end; ++n) {
         const uint64_t nonce = r.base + n;  // wraps mod 2^64 like the GPU strides
         const uint64_t v = host_work_value(j.pre.m, nonce);
-        if (v >= j.threshold) {
+        if (v >= j.threshold.load(std::memory_order_relaxed)) {  // (the current one: npow_retarget may raise it)
           std::lock_guard<std::mutex> g(sh.hit_mu);
           if (!sh.hit) {
             sh.hit = true;
@@ -111,7 +111,15 @@ void hash_job(CpuShared& sh, Device& d, const JobP& jp, size_t k) {
       std::lock_guard<std::mutex> sg(d.stats_mu);
       d.nonces += n;
     }
-    if (stopped) return;  // the rest of this claim is not hashed: the job is over for this device
+    if (stopped) {
+      // the rest of this claim is not hashed: the job is over for this device -- unless the hit turns out to be
+      // below a threshold raised meanwhile (cpu_worker_run drops it and hashes on), so the rest goes back
+      if (n < r.count) {
+        std::lock_guard<std::mutex> g(g_pool.mu);
+        j.todo[k].push_front({r.base + n, r.count - n});
+      }
+      return;
+    }
   }
 }
 
@@ -214,6 +222,16 @@ void cpu_worker_run(Device& d) {
       }
       if (g_release_delay_us > 0) std::this_thread::sleep_for(std::chrono::microseconds(g_release_delay_us));
       std::lock_guard<std::mutex> g(g_pool.mu);
+      {
+        // a hit below a threshold raised since the hasher compared it (npow_retarget, under this lock) is dropped
+        // like a GPU's stale win, and the job hashed on
+        std::lock_guard<std::mutex> hg(sh.hit_mu);
+        if (sh.hit && sh.hit_value < j->threshold.load(std::memory_order_relaxed) && !j->decided && !j->cancel_seen()) {
+          sh.hit = false;
+          sh.stop = false;
+          j->stale_wins++;
+        }
+      }
       again = !over(*j, sh) && g_pool.running && !j->todo[k].empty();
     }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -235,7 +253,8 @@ void cpu_worker_run(Device& d) {
     std::lock_guard<std::mutex> g(g_pool.mu);
     j->done += hashed;
     // re-validated like a GPU winner (the same function: a hit is valid by construction)
-    if (hit && host_work_value(j->pre.m, hn) == hv && hv >= j->threshold && j->status == kPending) {
+    if (hit && host_work_value(j->pre.m, hn) == hv && hv >= j->threshold.load(std::memory_order_relaxed) &&
+        j->status == kPending) {
       decide_locked(*j, NPOW_OK, hn, hv);
       j->t_decide = now_us();
       j->winner_k = (int)k;

@@ -746,6 +746,11 @@ int npow_promote(uint64_t ticket, uint32_t weight) try {
   return pool_promote(ticket, weight);
 } catch (...) { return guard_exception(); }
 
+int npow_retarget(uint64_t ticket, uint64_t threshold) try {
+  if (int rc = check_init()) return rc;
+  return pool_retarget(ticket, threshold);
+} catch (...) { return guard_exception(); }
+
 int npow_pool_config(uint32_t max_active) try {
   if (int rc = check_init()) return rc;
   return pool_set_max_active(max_active);

@@ -206,6 +206,7 @@ int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* va
 int pool_wait_result(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* value);
 int pool_cancel(uint64_t ticket);
 int pool_promote(uint64_t ticket, uint32_t weight);  // weight: 1, 2, 4 or 8 (npow_promote; checked by the caller)
+int pool_retarget(uint64_t ticket, uint64_t threshold);  // npow_retarget
 int pool_set_max_active(uint32_t n);
 void pool_counts(uint32_t* queued, uint32_t* active);
 

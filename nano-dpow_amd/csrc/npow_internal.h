@@ -189,6 +189,9 @@ struct PoolSlotCount {
 // entry in iterations that started after one of its waves knew the entry was over (its dead word, a win, or a
 // kill read by its poll), added when it leaves the entry.  Cumulative per slot like the done counts.
 constexpr int kLateWord = 1;
+// Word kStaleWord of the same lines: lanes whose value met the threshold their wave held but not the slot's floor
+// (npow_retarget, PoolFloor), refused in the hit branch.  Cumulative per slot like the other two.
+constexpr int kStaleWord = 2;
 // Workgroups that have left an uncounted (one-entry) launch, per launch ring (round 5): one counter per XCD
 // shard (workgroup index mod kWgsShards), then one over the shards, each on its own line -- the last one out
 // of a shard bumps `top`, the last one out of the launch publishes the entry's final count when the entry is
@@ -254,9 +257,21 @@ struct alignas(64) PoolFin {
   uint64_t t_join;   // ... and when a workgroup last started hashing the slot's entry
   uint64_t linger_gen;  // round 6: the generation whose kill a lingering workgroup relayed (ls2_linger_relay) --
                         // an entry left live with no workgroup on it; the host counts them (stats linger_relays)
-  uint8_t pad[8];
+  uint64_t stale;  // the slot's stale-hit words, summed (kStaleWord; cumulative, stored before gen like total and late)
 };
 static_assert(sizeof(PoolFin) == 64, "one line per slot");
+// The floor of a slot's threshold (npow_retarget): the host raised the threshold of the job that generation `gen`
+// of the slot searches.  It writes the threshold first and then releases the generation; a second raise for the
+// same generation is one 64-bit store of a larger threshold.  A wave reads the record only when it has a hit
+// (pool_body_ls2): the generation first and, if it is its entry's, then the threshold, both past the caches, and
+// takes the threshold as its own when it is above the one it holds.  A slot gets its next
+// generation only after every workgroup has left the previous one (its final count, or its launches' end), so no
+// wave of an older generation reads a record while the host rewrites it for a newer one; a record of another
+// generation is ignored.
+struct alignas(16) PoolFloor {
+  uint64_t threshold;
+  uint64_t gen;
+};
 // An unbounded job adopted while a search launch runs joins that launch instead of ending it
 // (a yield): the host writes its entry at ring position p (dyn[p % kDynRing]) and then releases
 // the low half of PoolMailbox::ctl = p + 1; the launch's entries are its table's n entries followed by positions
@@ -279,6 +294,7 @@ struct PoolMailbox {
   uint64_t kill[kMaxSlots];  // kill[s] = gen: the job in slot s (that generation) must stop
   uint64_t boost[kMaxSlots];  // boost[s] = pool_boost_word(gen, wsh): the job in slot s (that generation) was promoted
                               // to the weight of that shift (npow_promote; written before the counter below is bumped)
+  PoolFloor floor[kMaxSlots];  // floor[s]: the raised threshold of the job in slot s (npow_retarget; PoolFloor)
   // High half: bumped by the host when new jobs wait for the next launch (a yield); low half: the
   // dynamic entries published (ring positions, see PoolDynEntry).  One word, so a poll reads both
   // with one uncached read.

@@ -410,6 +410,11 @@ __device__ __forceinline__ void ls2_publish_fin(PoolDevState* st, PoolMailbox* m
   }
   __hip_atomic_store(&mb->fin[slot].total, (uint64_t)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(&mb->fin[slot].late, (uint64_t)late, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  unsigned long long stale = 0;  // (a loop of its own, after the two sums are stored: nothing more live beside them)
+#pragma unroll 1
+  for (int i = 0; i < kPoolDoneShards; ++i)
+    stale += __hip_atomic_load(&st->done[slot][i * 8 + kStaleWord], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&mb->fin[slot].stale, (uint64_t)stale, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(&mb->fin[slot].gen, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -450,12 +455,20 @@ __device__ __forceinline__ void ls2_fin_wave(PoolDevState* st, PoolMailbox* mb, 
   static_assert(kPoolDoneShards == 32, "one half-wave per counter");
   unsigned long long t = __hip_atomic_load(&st->done[slot][(lane & 31) * 8 + (lane < 32 ? 0 : kLateWord)],
                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // (the stale-hit words of the same lines, kStaleWord: lanes 0..31, loaded beside the first)
+  unsigned long long ts = lane < 32 ? __hip_atomic_load(&st->done[slot][lane * 8 + kStaleWord], __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT)
+                                    : 0ull;
 #pragma unroll
-  for (int m = 16; m >= 1; m >>= 1) t += __shfl_xor(t, m);
+  for (int m = 16; m >= 1; m >>= 1) {
+    t += __shfl_xor(t, m);
+    ts += __shfl_xor(ts, m);
+  }
   const unsigned long long t_late = readlane64(t, 32);
   if (lane == 0) {
     __hip_atomic_store(&mb->fin[slot].total, (uint64_t)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(&mb->fin[slot].late, (uint64_t)t_late, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&mb->fin[slot].stale, (uint64_t)ts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(&mb->fin[slot].t_fin, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(&mb->fin[slot].gen, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
@@ -1026,22 +1039,52 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
       } else {
         done += 64;
       }
-      const uint64_t hits = __ballot(hit);
+      uint64_t hits = __ballot(hit);
       // why the workgroup must leave the entry, as a stop-request kind (0 = not at all; the time budget files
       // kind 0 = end the launch): 1 = the entry was over before this hash started (its dead word), 2 = it is
       // over since this hash (a win; a kill read by this wave's poll), 3 = leave for another reason (a yield,
       // a move to a new entry).  The smallest kind of the earliest iteration wins, so the exit knows how many
       // of the workgroup's last hashes started after it knew the entry was over: 2 for kind 1, 1 for kind 2.
-      uint32_t why = hits != 0 ? 2u : 0u;
+      uint32_t why = 0u;
       if (__builtin_expect(hits != 0, 0)) {
-        const int wl = __builtin_ctzll(hits);
-        const uint64_t wn = readlane64(nonce, wl), wval = readlane64(value, wl);
-        if (lane == 0) {
-          // the entry's slot and generation re-read from it (c.up points at the entry): kept live for
-          // this rare branch they were spilled to scratch by every wave at every entry it joined
-          ConstEntry* ce = (ConstEntry*)(uintptr_t)c.up;
-          asm volatile("" : "+s"(ce));
-          ls2_publish_win(st, mb, ce->slot, ce->gen, wn, wval);
+        // the entry's slot and generation re-read from it (c.up points at the entry): kept live for
+        // this rare branch they were spilled to scratch by every wave at every entry it joined
+        ConstEntry* ce = (ConstEntry*)(uintptr_t)c.up;
+        asm volatile("" : "+s"(ce));
+        const uint32_t wslot = ce->slot;
+        const uint64_t wgen = ce->gen;
+        // Retargeting (npow_retarget, PoolFloor): the host may have raised the job's threshold since this wave
+        // loaded it.  The slot's floor record is read here, where a wave has a hit -- about once per search -- and
+        // nowhere else: the generation, then (after it has arrived) the threshold, past the caches, the same
+        // words in every lane.  A record of this entry's generation above the wave's threshold becomes the wave's
+        // threshold from here on; the lanes that no longer qualify are refused and counted (kStaleWord), and a
+        // wave left without a hit goes on hashing: no dead word, no win record, no stop request.  A record of
+        // another generation, or not above, changes nothing.  (The microseconds between the host's store and this
+        // read are the host's to catch: Worker::handle_win re-arms a win below the job's threshold.)
+        // (a search that was never retargeted -- nearly every one -- finds another generation's tag, or none, and
+        // pays for that one read only: the threshold is read when the tag is the entry's)
+        PoolFloor* const fl = &mb->floor[wslot];
+        const uint64_t fgen = __hip_atomic_load(&fl->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        ls2_complete();
+        uint64_t floor = 0;
+        if (uni64(fgen) == wgen) {
+          const uint64_t fthr = __hip_atomic_load(&fl->threshold, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          ls2_complete();
+          floor = uni64(fthr);
+        }
+        if (floor > thr) {
+          c.threshold = floor;
+          const uint64_t keep = hits & __ballot(value >= floor);  // (hits: under the BOUNDED lane mask)
+          if (lane == 0)
+            atomicAdd(&st->done[wslot][(blockIdx.x % kPoolDoneShards) * 8 + kStaleWord],
+                      (unsigned long long)__builtin_popcountll(hits & ~keep));
+          hits = keep;
+        }
+        if (hits != 0) {
+          why = 2u;
+          const int wl = __builtin_ctzll(hits);
+          const uint64_t wn = readlane64(nonce, wl), wval = readlane64(value, wl);
+          if (lane == 0) ls2_publish_win(st, mb, wslot, wgen, wn, wval);
         }
       }
       // which wave polls at iteration it0: the one with w = -it0 * kPollStride (mod poll_mask + 1) -- consecutive

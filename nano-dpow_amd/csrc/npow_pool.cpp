@@ -36,7 +36,9 @@
 // Test hooks (environment, read once, and only with NANOPOW_TEST_HOOKS=1 beside them -- a stray
 // variable in a deployment must not drop GPUs; an active hook is reported on stderr):
 // NANOPOW_FAULT_INVALID=d[,d...] makes the host read a corrupted value for every win of those
-// logical devices; NANOPOW_FAULT_HIP=d:n makes device d's launches fail after its n-th.
+// logical devices; NANOPOW_FAULT_HIP=d:n makes device d's launches fail after its n-th;
+// NANOPOW_FAULT_RETARGET_BLIND=1 makes pool_retarget skip the slots' floor records, so a running launch learns of
+// a raise only through the host's refusal of its win (handle_win's stale path).
 // (npow_engine.cpp: NANOPOW_FAULT_INIT=d fails npow_init on d.)
 #include <hip/hip_runtime.h>
 #include <sys/prctl.h>
@@ -134,6 +136,7 @@ struct Faults {
   uint64_t invalid_mask = 0;  // logical devices whose wins read back corrupted
   int hip_dev = -1;           // logical device whose launches fail ...
   uint64_t hip_after = 0;     // ... after this many
+  bool retarget_blind = false;  // pool_retarget writes no floor record
 };
 }  // namespace
 bool test_hooks_enabled() {
@@ -148,7 +151,7 @@ const Faults& faults() {
   static const Faults f = [] {
     Faults x;
     if (!test_hooks_enabled()) {
-      if (getenv("NANOPOW_FAULT_INVALID") || getenv("NANOPOW_FAULT_HIP"))
+      if (getenv("NANOPOW_FAULT_INVALID") || getenv("NANOPOW_FAULT_HIP") || getenv("NANOPOW_FAULT_RETARGET_BLIND"))
         fprintf(stderr, "nanopow: NANOPOW_FAULT_* ignored (test hooks need NANOPOW_TEST_HOOKS=1)\n");
       return x;
     }
@@ -166,9 +169,11 @@ const Faults& faults() {
       x.hip_dev = (int)strtol(e, &end, 10);
       if (end && *end == ':') x.hip_after = strtoull(end + 1, nullptr, 10);
     }
+    if (const char* e = getenv("NANOPOW_FAULT_RETARGET_BLIND")) x.retarget_blind = strcmp(e, "1") == 0;
     if (x.invalid_mask || x.hip_dev >= 0)
       fprintf(stderr, "nanopow: TEST HOOKS ACTIVE: corrupt wins of device mask %#llx, fail launches of device %d after %llu\n",
               (unsigned long long)x.invalid_mask, x.hip_dev, (unsigned long long)x.hip_after);
+    if (x.retarget_blind) fprintf(stderr, "nanopow: TEST HOOKS ACTIVE: retargets write no floor record\n");
     return x;
   }();
   return f;
@@ -442,7 +447,7 @@ static double spin_window_us(const Job& j) {
     const Device& d = *g_devs[(size_t)id];
     if (!d.cpu_threads) rate += d.cus * kNoncesPerCuUs;
   }
-  const double expect = 18446744073709551616.0 / (18446744073709551616.0 - (double)j.threshold + 1.0);
+  const double expect = 18446744073709551616.0 / (18446744073709551616.0 - (double)j.threshold.load() + 1.0);
   const double w = rate > 0 ? 3.0 * expect / rate : kWatchSpinMaxUs;
   return std::min(kWatchSpinMaxUs, std::max(kWatchSpinUs, w));
 }
@@ -507,10 +512,13 @@ void watch_handle(Device& d, int s, uint64_t gen) {
   uint64_t v = __atomic_load_n(&pw.value, __ATOMIC_RELAXED);
   if (__atomic_load_n(&pw.gen, __ATOMIC_ACQUIRE) != gen) return;  // the record moved on meanwhile
   if ((faults().invalid_mask >> d.id) & 1) v ^= 1;                 // NANOPOW_FAULT_INVALID (tests)
-  if (host_work_value(j->pre.m, n) != v || v < j->threshold) return;  // invalid: the worker's business
+  if (host_work_value(j->pre.m, n) != v || v < j->threshold.load(std::memory_order_relaxed))
+    return;  // invalid, or below a raised threshold (npow_retarget): the worker's business
   PoolLock g;  // (j, a local reference, outlives it)
   const int k = index_in(*j, d.id);
   if (j->status != kPending || k < 0 || j->dev_gen[(size_t)k] != gen) return;
+  if (v < j->threshold.load(std::memory_order_relaxed)) return;  // raised since the look above (pool_retarget holds
+                                                                 // this lock): a decision never undercuts a raise
   decide_locked(*j, NPOW_OK, n, v);
   j->t_decide = now_us();
   j->t_win_seen = t_seen;
@@ -598,6 +606,7 @@ struct Slot {
   uint64_t gen = 0;
   uint64_t baseline = 0;   // done counter of this slot index at its last retirement
   uint64_t late_base = 0;  // ... and its late counter (kLateWord)
+  uint64_t stale_base = 0;  // ... and its stale-hit counter (kStaleWord)
   bool win_seen = false;
   bool requeue = false;    // invalid GPU result: hand the job back to this device after retiring
   bool no_more = false;    // bounded range fully issued
@@ -899,7 +908,8 @@ void Worker::handle_win(int s) {
   const uint64_t cpu_v = host_work_value(j.pre.m, n);
   PoolLock g;  // (the slot holds the job)
   if (j.t_win == 0) j.t_win = t_seen;
-  if (cpu_v == v && v >= j.threshold) {
+  const uint64_t threshold = j.threshold.load(std::memory_order_relaxed);  // (under the lock: pool_retarget)
+  if (cpu_v == v && v >= threshold) {
     invalid_streak_ = 0;
     if (j.status == kPending) {
       decide_locked(j, NPOW_OK, n, v);
@@ -913,12 +923,24 @@ void Worker::handle_win(int s) {
     // "GPU returned invalid work": the launches that held this generation stopped at the win,
     // so a bounded job gets back every range from the one holding the winner on; the job is
     // re-armed on this device after the slot retires.  The third in a row drops the device.
-    {
-      std::lock_guard<std::mutex> sg(d_.stats_mu);
-      d_.invalid++;
+    // A stale win -- the value is the CPU's, but below a threshold raised while the search ran (npow_retarget; the
+    // wave read the slot's floor record before the host's store landed, or never could: a dropped record) -- is
+    // correct work at the wrong difficulty, not a fault: it takes the same way back without touching the
+    // device's invalid count or its streak.  (Only a job whose threshold was raised: a correct value below a
+    // threshold that never moved is a kernel's fault like any other.)
+    const bool stale = cpu_v == v && j.retargets > 0;
+    if (stale) {
+      j.stale_wins++;
+      NPOW_DBGT("nanopow[%d]: slot %d g%llu: win %016llx below the raised threshold, re-armed\n", d_.id, s,
+                (unsigned long long)sl.gen, (unsigned long long)v);
+    } else {
+      {
+        std::lock_guard<std::mutex> sg(d_.stats_mu);
+        d_.invalid++;
+      }
+      fprintf(stderr, "nanopow: GPU %d returned invalid work %016llx (value %016llx, cpu %016llx)\n", d_.id,
+              (unsigned long long)n, (unsigned long long)v, (unsigned long long)cpu_v);
     }
-    fprintf(stderr, "nanopow: GPU %d returned invalid work %016llx (value %016llx, cpu %016llx)\n", d_.id,
-            (unsigned long long)n, (unsigned long long)v, (unsigned long long)cpu_v);
     if (j.max_per_dev) {
       size_t from = 0;
       for (size_t i = 0; i < sl.inflight.size(); ++i)
@@ -929,7 +951,7 @@ void Worker::handle_win(int s) {
       push_back_locked(sl, from);
     }
     sl.requeue = true;
-    if (++invalid_streak_ >= kInvalidStreakMax && !d_.dead) {
+    if (!stale && ++invalid_streak_ >= kInvalidStreakMax && !d_.dead) {
       d_.dead_code = NPOW_ERR_INVALID_WORK;
       d_.dead_msg = "GPU " + std::to_string(d_.id) + " returned invalid work " + std::to_string(kInvalidStreakMax) +
                     " consecutive times";
@@ -1025,6 +1047,7 @@ void Worker::early_finish(int s) {
   if (win_published(s)) handle_win(s);  // the winner released its record before closing the entry
   const uint64_t total = __atomic_load_n(&d_.pmb->fin[s].total, __ATOMIC_RELAXED);
   const uint64_t late = __atomic_load_n(&d_.pmb->fin[s].late, __ATOMIC_RELAXED);
+  const uint64_t stale_hits = __atomic_load_n(&d_.pmb->fin[s].stale, __ATOMIC_RELAXED);
   PoolLock g;  // (the slot holds the job)
   Job& j = *sl.job;
   if (g_trace_lat && j.gpu_t_win) {  // GPU timeline (one GPU's clock: CU partitions), from the deciding win
@@ -1062,11 +1085,13 @@ void Worker::early_finish(int s) {
   sl.baseline = total;  // retire() then reads back the same total: a delta of 0
   j.done += delta;
   j.late[sl.k] += late - sl.late_base;
+  j.stale_hits += stale_hits - sl.stale_base;
   {
     std::lock_guard<std::mutex> sg(d_.stats_mu);
     d_.late += late - sl.late_base;
   }
   sl.late_base = late;
+  sl.stale_base = stale_hits;
   if (g_trace_lat && j.t_kend == 0) j.t_kend = now_us();
   {
     std::lock_guard<std::mutex> sg(d_.stats_mu);
@@ -1408,14 +1433,17 @@ int Worker::retire() {
     if (e == hipErrorNotReady) continue;
     if (e != hipSuccess) return fail(NPOW_ERR_HIP, std::string("pool read-back: ") + hipGetErrorString(e));
     // every launch that held the slot has completed: its done shards are final
-    uint64_t sum = 0, late = 0;
+    uint64_t sum = 0, late = 0, stale_hits = 0;
     for (int i = 0; i < kPoolDoneShards; ++i) {
       sum += d_.h_done[(size_t)s * row + i * 8];
       late += d_.h_done[(size_t)s * row + i * 8 + kLateWord];
+      stale_hits += d_.h_done[(size_t)s * row + i * 8 + kStaleWord];
     }
     const uint64_t delta = sum - sl.baseline, late_delta = late - sl.late_base;
+    const uint64_t stale_delta = stale_hits - sl.stale_base;  // (0 for a slot finished from its final count)
     sl.baseline = sum;
     sl.late_base = late;
+    sl.stale_base = stale_hits;
     {
       std::lock_guard<std::mutex> sg(d_.stats_mu);
       d_.nonces += delta;
@@ -1449,6 +1477,7 @@ int Worker::retire() {
       Job& j = *sl.job;
       j.done += delta;
       j.late[sl.k] += late_delta;
+      j.stale_hits += stale_delta;
       if (d_.dead) {
         abandon_locked(sl.job, sl.k, d_.dead_code, d_.dead_msg);  // survivors take what is left
       } else if (!j.decided && (sl.requeue || !j.todo[sl.k].empty())) {
@@ -1966,6 +1995,9 @@ int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* va
     }
     info->launch_all_us = since(all);
     info->win_seen_us = since(j->t_win_seen);
+    info->retargets = j->retargets;
+    info->stale_hits = j->stale_hits;
+    info->stale_wins = j->stale_wins;
   }
   if (g_trace_lat) {
     fprintf(stderr, "nanopow-lat adopt %.1f launch %.1f win %.1f kend %.1f finish %.1f return %.1f", j->t_adopt - j->t_submit,
@@ -2062,6 +2094,42 @@ int pool_promote(uint64_t ticket, uint32_t weight) {
     if (d.counted_inflight.load(std::memory_order_acquire) > 0 && j->t_launch_dev[k] != 0) {
       std::lock_guard<std::mutex> sg(d.stats_mu);
       d.promotions++;
+    }
+  }
+  return NPOW_OK;
+}
+
+// Raise a job's threshold (npow_retarget).  Only the pool lock, as pool_promote: nothing here waits for a GPU, and
+// the lock orders the raise against every decision (decide_locked is called under it, and the win watcher and
+// handle_win compare a win with the threshold under it): once this returns NPOW_OK no result below the threshold
+// can be decided.  The field is all a waiting job needs, or one no slot holds yet: every table and dynamic entry
+// built from now on carries it, and the CPU workers read it at each check.  For each GPU that holds the job in a
+// slot the slot's floor record is written (PoolFloor: the threshold, then the generation with release; the same
+// generation again: one store of the larger threshold), which a wave of a running launch reads when it has a hit
+// (npow_kernel.hip pool_body_ls2) -- no launch ends, and the entry keeps its slot, generation, weight and nonce
+// position.  A win a wave published before it could see the record is refused by handle_win (stale_wins).
+int pool_retarget(uint64_t ticket, uint64_t threshold) {
+  std::lock_guard<std::mutex> g(g_pool.mu);
+  auto it = g_pool.tickets.find(ticket);
+  if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  const JobP& j = it->second;
+  if (threshold <= j->threshold.load(std::memory_order_relaxed)) return NPOW_OK;  // never lowered
+  if (j->finished || j->decided || j->cancel_seen()) return NPOW_TOO_LATE;        // its outcome stands
+  j->threshold.store(threshold, std::memory_order_release);
+  j->retargets++;
+  // (Job::spin_us stays as the submit set it: waiters read it without the lock, and a window sized for the old
+  // threshold only puts a longer search's waiter and watcher to sleep sooner)
+  if (!j->admitted || faults().retarget_blind) return NPOW_OK;
+  for (size_t k = 0; k < j->devs.size(); ++k) {
+    if (!j->on_dev[k] || j->dev_slot[k] < 0) continue;  // (not adopted yet; the CPU device has no slot)
+    Device& d = *g_devs[(size_t)j->devs[k]];
+    if (d.cpu_threads || !d.pmb) continue;
+    PoolFloor& f = d.pmb->floor[j->dev_slot[k]];
+    if (__atomic_load_n(&f.gen, __ATOMIC_RELAXED) != j->dev_gen[k]) {
+      __atomic_store_n(&f.threshold, threshold, __ATOMIC_RELAXED);
+      __atomic_store_n(&f.gen, j->dev_gen[k], __ATOMIC_RELEASE);  // after the threshold
+    } else {
+      __atomic_store_n(&f.threshold, threshold, __ATOMIC_RELEASE);
     }
   }
   return NPOW_OK;

@@ -26,7 +26,9 @@ struct Job {
   uint64_t ticket = 0;
   RootPrecomp pre{};
   uint64_t u[NPOW_ASM_N_UNIFORMS] = {};
-  uint64_t threshold = 0, start = 0, max_per_dev = 0, spacing = 0;
+  std::atomic<uint64_t> threshold{0};  // written under g_pool.mu (pool_submit, pool_retarget: it only rises); the
+                                       // win watcher, the GPU workers and the CPU workers read it without the lock
+  uint64_t start = 0, max_per_dev = 0, spacing = 0;
   const volatile uint32_t* cancel = nullptr;
   uint32_t weight = 1;    // 1, 2, 4 or 8 (npow_submit_weighted): its share of each GPU's workgroups among the live
                           // unbounded jobs, and its place in the admission queue; the CPU device ignores it
@@ -43,6 +45,9 @@ struct Job {
   std::vector<double> t_launch_dev; // per device k: when its first launch holding the job was issued (us; 0 = none)
   std::vector<uint64_t> late;       // per device k: nonces its waves hashed after they knew the job was over
                                     // (device-side count, PoolDevState kLateWord)
+  uint64_t retargets = 0;           // raises of the threshold that took effect (pool_retarget)
+  uint64_t stale_hits = 0;          // lanes the devices' waves refused: below the slot's floor (kStaleWord)
+  uint64_t stale_wins = 0;          // wins published under an older threshold, refused and re-armed (handle_win)
   int winner_k = -1;                // the device whose result decided the job
   int pending_devs = 0;
   std::atomic<bool> admitted{false};  // written under g_pool.mu; waiters read it without it

@@ -22,6 +22,7 @@ NPOW_OK = 0
 NPOW_CANCELLED = 1
 NPOW_EXHAUSTED = 2
 NPOW_PENDING = 3
+NPOW_TOO_LATE = 4  # npow_retarget: the search was already decided or cancelled (not yet collected)
 NPOW_ERR_NOT_INITIALISED = -1
 NPOW_ERR_NO_DEVICE = -2
 NPOW_ERR_BAD_ARGUMENT = -3
@@ -46,7 +47,7 @@ EXPORTED_SYMBOLS = (
     "npow_submit", "npow_wait", "npow_cancel", "npow_pool_config", "npow_pool_status",
     "npow_set_pool_tuning", "npow_values_path", "npow_wait_info", "npow_device_stats_get_sized",
     "npow_abi_version", "npow_config_cpu_threads", "npow_wait_result", "npow_submit_weighted",
-    "npow_promote",
+    "npow_promote", "npow_retarget",
 )
 
 
@@ -114,6 +115,9 @@ class SearchInfo(ctypes.Structure):
         ("launch_us", ctypes.c_double),
         ("launch_all_us", ctypes.c_double),
         ("win_seen_us", ctypes.c_double),
+        ("retargets", ctypes.c_uint64),           # ABI 7, with npow_retarget
+        ("stale_hits", ctypes.c_uint64),
+        ("stale_wins", ctypes.c_uint64),
     ]
 
 
@@ -211,6 +215,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         if hasattr(lib, "npow_promote"):  # added within ABI 7: probed for
             lib.npow_promote.argtypes = [u64, u32]
             lib.npow_promote.restype = ctypes.c_int
+        if hasattr(lib, "npow_retarget"):  # added within ABI 7: probed for
+            lib.npow_retarget.argtypes = [u64, u64]
+            lib.npow_retarget.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -330,6 +337,22 @@ class Ticket:
         if self.result is not None:
             raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
         _check(lib.npow_promote(self.ticket, weight), lib)
+
+    def retarget(self, threshold: int) -> bool:
+        """Raise the search's threshold to max(current, threshold) in place (npow_retarget): a waiting search is
+        admitted with it, a running one keeps its slot, weight and nonce position and passes over hits that no
+        longer qualify.  True when it holds -- every result the ticket returns from now on has a value at or
+        above `threshold` -- and False when it came too late (NPOW_TOO_LATE: the search was already decided or
+        cancelled; its result stands).  NanoPowError(NPOW_ERR_BAD_ARGUMENT) for a threshold outside 64 bits, a
+        collected ticket -- and when the loaded library has no npow_retarget."""
+        lib = self.engine.lib
+        if not hasattr(lib, "npow_retarget"):
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_retarget")
+        if not isinstance(threshold, int) or isinstance(threshold, bool) or not 0 <= threshold <= M64:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "threshold must be an integer in [0, 2^64)")
+        if self.result is not None:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
+        return _check(lib.npow_retarget(self.ticket, threshold), lib, ok=(NPOW_OK, NPOW_TOO_LATE)) == NPOW_OK
 
     def __del__(self) -> None:
         # An abandoned ticket: cancel its search and collect it, so the engine forgets the job

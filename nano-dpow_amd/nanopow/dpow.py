@@ -31,6 +31,16 @@ and its difficulty is not above it, a queued hash is retyped to the heavier type
 one is raised at the work server (``work_promote``, nanopow.server) -- its running search gets
 the heavier share at once -- and its result is published under the heavier type.  With the
 default weights (all 1) nothing is heavier: the message is ignored as in the reference.
+
+Retargeting, opt-in (``retarget=True``): the hub asks for on-demand work above the precache
+difficulty whenever a service sends a multiplier (server/dpow_server.py:273-328), and a precache
+result below it would be rejected.  A message for a known hash at a HIGHER difficulty then
+replaces a queued hash's difficulty, and for an ongoing hash is passed to the work server as
+``work_retarget`` (nanopow.server: the running search goes on in place at the higher difficulty),
+with a ``work_promote`` beside it when the type is heavier too.  The handler records the new
+difficulty; a reply whose ``difficulty`` is below it means the raise came too late, and the hash
+is queued again at the recorded difficulty instead of being published.  Without the option such
+a message is ignored as before.
 """
 from __future__ import annotations
 
@@ -132,6 +142,13 @@ class _Ongoing(dict):
         self.pop(block_hash, None)
 
 
+def _difficulty_above(new: str, old: str) -> bool:
+    try:
+        return int(new, 16) > int(old, 16)
+    except ValueError:
+        return False
+
+
 def _difficulty_not_above(new: str, old: str) -> bool:
     try:
         return int(new, 16) <= int(old, 16)
@@ -143,11 +160,13 @@ class DpowWorkHandler:
     """WorkHandler-equivalent: queue of requests -> work server -> published results."""
 
     def __init__(self, worker: HttpWorker, publish: PublishFn, payout: str, concurrency: int = 1,
-                 rng: Optional[random.Random] = None, weights: Optional[Dict[str, int]] = None) -> None:
+                 rng: Optional[random.Random] = None, weights: Optional[Dict[str, int]] = None,
+                 retarget: bool = False) -> None:
         self.weights = dict(DEFAULT_WEIGHTS if weights is None else weights)
         for t, w in self.weights.items():
             if w not in (1, 2, 4, 8):
                 raise ValueError(f"weight of work type {t!r} must be 1, 2, 4 or 8, not {w!r}")
+        self.retarget = retarget
         self.worker = worker
         self.publish = publish
         self.payout = payout
@@ -157,7 +176,8 @@ class DpowWorkHandler:
         self.ongoing: _Ongoing = _Ongoing()
         self._ready = asyncio.Event()
         self._tasks = []
-        self.stats = {"queued": 0, "ignored": 0, "sent": 0, "cancelled": 0, "errors": 0, "promoted": 0}
+        self.stats = {"queued": 0, "ignored": 0, "sent": 0, "cancelled": 0, "errors": 0, "promoted": 0,
+                      "retargeted": 0, "requeued": 0}
 
     async def start(self) -> None:
         # WorkHandler.start: the probe must answer with an "error" field (work_handler.py:53)
@@ -192,6 +212,9 @@ class DpowWorkHandler:
             queued = block_hash in self.queue
             old_difficulty, old_type = self.queue[block_hash] if queued else self.ongoing[block_hash]
             weight = self.weights.get(work_type, 1)
+            if self.retarget and _difficulty_above(difficulty, old_difficulty):
+                await self._retarget(block_hash, queued, work_type, difficulty)
+                return
             if weight <= self.weights.get(old_type, 1) or not _difficulty_not_above(difficulty, old_difficulty):
                 self.stats["ignored"] += 1
                 return
@@ -208,6 +231,27 @@ class DpowWorkHandler:
         self.queue[block_hash] = (difficulty, work_type)
         self.stats["queued"] += 1
         self._ready.set()
+
+    async def _retarget(self, block_hash: str, queued: bool, work_type: str, difficulty: str) -> None:
+        """The same hash again at a higher difficulty (module docstring; ``retarget=True``)."""
+        old_type = (self.queue[block_hash] if queued else self.ongoing[block_hash])[1]
+        weight = self.weights.get(work_type, 1)
+        heavier = weight > self.weights.get(old_type, 1)
+        self.stats["retargeted"] += 1
+        if heavier:
+            self.stats["promoted"] += 1
+        if queued:
+            self.queue[block_hash] = (difficulty, work_type if heavier else old_type)
+            return
+        self.ongoing[block_hash][0] = difficulty  # a reply below it is not published (_loop)
+        if heavier:
+            self.ongoing[block_hash][1] = work_type
+        try:
+            await self.worker.post({"action": "work_retarget", "hash": block_hash, "difficulty": difficulty})
+            if heavier:
+                await self.worker.post({"action": "work_promote", "hash": block_hash, "weight": weight})
+        except Exception as e:  # noqa: BLE001 -- a reply below the recorded difficulty is queued again
+            log.error("Work handler retarget error: %s", e)
 
     async def queue_cancel(self, block_hash: str) -> None:
         if self.queue.pop(block_hash, None) is not None:
@@ -246,8 +290,13 @@ class DpowWorkHandler:
                 continue
             if block_hash not in self.ongoing:  # cancelled meanwhile
                 continue
-            work_type = self.ongoing.pop(block_hash)[1]  # (a promotion may have raised it)
-            if "work" in res:
+            difficulty, work_type = self.ongoing.pop(block_hash)  # (a promotion or a retarget may have raised them)
+            if "work" in res and self.retarget and _difficulty_above(difficulty, str(res.get("difficulty", difficulty))):
+                # the raise came too late for that search: again, at the recorded difficulty
+                self.queue[block_hash] = (difficulty, work_type)
+                self.stats["requeued"] += 1
+                self._ready.set()
+            elif "work" in res:
                 await self.publish(*result_message(work_type, block_hash, res["work"], self.payout))
                 self.stats["sent"] += 1
             elif res.get("error"):

@@ -29,6 +29,13 @@ search is already running (npow_promote: the share changes inside the running
 launch), and ``{"action": "work_promote", "hash": ..., "weight": ...}`` -- this
 server's extension too, answered ``{}`` like ``work_cancel`` whether or not a job
 matched -- raises every queued or running job of that hash.  Weights only rise.
+``{"action": "work_retarget", "hash": ..., "difficulty": ...}`` (or ``"multiplier"``, as in
+``work_generate``; this server's extension, answered ``{}`` likewise) raises the
+difficulty of every queued or running job of that hash that is below it: a running
+search goes on in place at the higher difficulty (npow_retarget) instead of being
+cancelled and started again, and a later ``work_generate`` at that difficulty joins
+it.  Difficulties only rise; ``work_generate`` itself still matches a job by hash and
+difficulty and never retargets one.
 The reference serves one request at a time; here up to ``max_active`` queued
 requests are handed to libnanopow's work pool at once (npow_submit), where
 every selected GPU searches all of them in the same kernel launches, so a
@@ -191,6 +198,8 @@ class WorkServer:
                 return self.work_cancel(req)
             if action == "work_promote":
                 return self.work_promote(req)
+            if action == "work_retarget":
+                return self.work_retarget(req)
             if action == "work_validate":
                 return self.work_validate(req)
             if action == "status":
@@ -252,6 +261,40 @@ class WorkServer:
             t.promote(weight)
         except Exception as e:  # (its search ended and was collected meanwhile: nothing to raise)
             log.debug("promote %s: %s", job.root.hex().upper(), e)
+
+    def work_retarget(self, req: Dict[str, Any]) -> Dict[str, Any]:
+        """Raise every queued or in-flight job of the hash that is below the difficulty to it (this server's
+        extension).  A job still waiting here, or one whose submit is under way (_submit compares again once the
+        ticket exists), only changes its field; one in the engine is retargeted there (_retarget, once the lock is
+        released) and its field follows when the raise held."""
+        root = W.parse_hash(req)
+        threshold = W.requested_threshold(req, self.base)
+        in_engine = []
+        with self._lock:
+            for j in self._inflight + self._queue:
+                if j.root != root or j.cancel.is_set or j.threshold >= threshold:
+                    continue
+                if j.active and j.ticket is not None:
+                    in_engine.append(j)
+                else:
+                    j.threshold = threshold
+        for j in in_engine:
+            self._retarget(j, threshold)
+        log.info("Retarget %s to difficulty %016x", root.hex().upper(), threshold)
+        return {}
+
+    def _retarget(self, job: Job, threshold: int) -> None:
+        t = job.ticket
+        if t is None or not hasattr(t, "retarget"):  # an engine without retargeting keeps serving
+            return
+        try:
+            held = t.retarget(threshold)
+        except Exception as e:  # (its search ended and was collected meanwhile: nothing to raise)
+            log.debug("retarget %s: %s", job.root.hex().upper(), e)
+            return
+        if held:  # (False: decided already -- its reply, at the old difficulty, is on its way)
+            with self._lock:
+                job.threshold = max(job.threshold, threshold)
 
     def work_validate(self, req: Dict[str, Any]) -> Dict[str, Any]:
         root = W.parse_hash(req)
@@ -333,15 +376,17 @@ class WorkServer:
         for job in jobs:
             try:
                 # (the keyword only for a weighted request: engines without it keep serving the others)
-                sent = job.weight
+                sent, sent_threshold = job.weight, job.threshold
                 extra = {"weight": sent} if sent != 1 else {}
-                ticket = self.engine.submit(job.root, job.threshold, start=self.rng.getrandbits(64),
+                ticket = self.engine.submit(job.root, sent_threshold, start=self.rng.getrandbits(64),
                                             device_mask=self.device_mask, cancel=job.cancel, **extra)
-                with self._lock:  # (a heavier duplicate may have come while the submit was under way)
+                with self._lock:  # (a heavier duplicate or a work_retarget may have come while the submit was under way)
                     job.ticket = ticket
-                    now = job.weight
+                    now, now_threshold = job.weight, job.threshold
                 if now > sent:
                     self._promote(job, now)
+                if now_threshold > sent_threshold:
+                    self._retarget(job, now_threshold)
             except Exception as e:  # never leave a client waiting
                 log.error("Error computing work: %s", e)
                 self._complete(job, dict(GENERATION_FAILED))

@@ -82,6 +82,14 @@ static void tickets(int tid, int n) {
       rc = npow_promote(ticket, 8);
       CHECK(rc == NPOW_OK, "promote rc %d", rc);
     }
+    // every fourth receive-difficulty ticket retargeted while it waits or runs (npow_retarget: the job's atomic
+    // threshold, the slots' floor records); a result after NPOW_OK must meet the raised threshold
+    uint64_t want = thr;
+    if (i % 4 == 2 && i % 3 != 0) {
+      rc = npow_retarget(ticket, 0xffffff8000000000ull);
+      CHECK(rc == NPOW_OK || rc == NPOW_TOO_LATE, "retarget rc %d", rc);
+      if (rc == NPOW_OK) want = 0xffffff8000000000ull;
+    }
     uint64_t nonce = 0, value = 0, done = 0;
     rc = npow_wait(ticket, 2000, &nonce, &value, &done);
     if (rc == NPOW_PENDING) {
@@ -90,7 +98,7 @@ static void tickets(int tid, int n) {
       rc = npow_wait(ticket, -1, &nonce, &value, &done);
     }
     CHECK(rc == NPOW_OK || rc == NPOW_CANCELLED, "ticket rc %d", rc);
-    if (rc == NPOW_OK) CHECK(value == npow_work_value(root, nonce) && value >= thr, "ticket value");
+    if (rc == NPOW_OK) CHECK(value == npow_work_value(root, nonce) && value >= want, "ticket value");
     (rc == NPOW_OK ? g_won : g_cancelled)++;
   }
 }
