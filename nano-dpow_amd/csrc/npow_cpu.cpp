@@ -15,7 +15,7 @@
 //     hashing threads, watches for the job's decision or cancellation every 100 us, and releases the
 //     jobs other devices decided before it got to them (so a GPU-won job does not wait for the CPU);
 //   * each hashing thread claims ranges of kCpuClaim nonces from the front of the job's queue for this
-//     device (Job::todo, under g_pool.mu: a dropped GPU's remainder may be re-strided here) and hashes
+//     device (JobDev::todo, under g_pool.mu: a dropped GPU's remainder may be re-strided here) and hashes
 //     them, testing the stop conditions every 256 nonces; a hit stops all of them.
 // A bounded job's ranges are hashed exactly once, so exhaustion and nonces_done stay exact.
 #include <algorithm>
@@ -73,12 +73,13 @@ void hash_job(CpuShared& sh, Device& d, const JobP& jp, size_t k) {
     Range r{0, 0};
     {
       std::lock_guard<std::mutex> g(g_pool.mu);
-      if (over(j, sh) || j.todo[k].empty()) return;
-      Range& f = j.todo[k].front();
+      std::deque<Range>& todo = j.dev[k].todo;
+      if (over(j, sh) || todo.empty()) return;
+      Range& f = todo.front();
       r = {f.base, std::min(f.count, kCpuClaim)};
       f.base += r.count;
       f.count -= r.count;
-      if (f.count == 0) j.todo[k].pop_front();
+      if (f.count == 0) todo.pop_front();
     }
     uint64_t n = 0;
     bool stopped = false;
@@ -116,7 +117,7 @@ void hash_job(CpuShared& sh, Device& d, const JobP& jp, size_t k) {
       // below a threshold raised meanwhile (cpu_worker_run drops it and hashes on), so the rest goes back
       if (n < r.count) {
         std::lock_guard<std::mutex> g(g_pool.mu);
-        j.todo[k].push_front({r.base + n, r.count - n});
+        j.dev[k].todo.push_front({r.base + n, r.count - n});
       }
       return;
     }
@@ -147,8 +148,8 @@ void hasher(CpuShared& sh, Device& d) {
 void release_unadopted_locked(int dev) {
   for (const JobP& j : std::vector<JobP>(g_pool.active)) {  // copy: device_done_locked may erase
     const int k = index_in(*j, dev);
-    if (k < 0 || j->on_dev[(size_t)k] || j->dev_done[(size_t)k]) continue;
-    if (j->decided || j->todo[(size_t)k].empty()) device_done_locked(j, (size_t)k);
+    if (k < 0 || j->dev[(size_t)k].on || j->dev[(size_t)k].done) continue;
+    if (j->decided || j->dev[(size_t)k].todo.empty()) device_done_locked(j, (size_t)k);
   }
 }
 
@@ -172,7 +173,7 @@ void cpu_worker_run(Device& d) {
       if (!g_pool.running || g_exiting.load()) break;
       for (const JobP& c : g_pool.active) {  // the oldest live job that wants this device
         const int kk = index_in(*c, d.id);
-        if (kk >= 0 && !c->on_dev[(size_t)kk] && !c->dev_done[(size_t)kk]) {
+        if (kk >= 0 && !c->dev[(size_t)kk].on && !c->dev[(size_t)kk].done) {
           j = c;
           k = (size_t)kk;
           break;
@@ -183,11 +184,11 @@ void cpu_worker_run(Device& d) {
         g_pool.cv_work.wait(lk, [&] { return !g_pool.running || g_exiting.load() || wants_device_locked(d.id); });
         continue;
       }
-      j->on_dev[k] = 1;
-      j->seen_dev[k] = 1;
-      j->dev_slot[k] = -1;  // no kill word: the hashers read the job's decision themselves
+      j->dev[k].on = true;
+      j->dev[k].seen = true;
+      j->dev[k].slot = -1;  // no kill word: the hashers read the job's decision themselves
       if (j->t_launch == 0) j->t_launch = now_us();
-      if (j->t_launch_dev[k] == 0) j->t_launch_dev[k] = now_us();
+      if (j->dev[k].t_launch == 0) j->dev[k].t_launch = now_us();
     }
     d.worker_busy.store(true, std::memory_order_release);
     d.active_slots.store(1, std::memory_order_release);
@@ -232,7 +233,7 @@ void cpu_worker_run(Device& d) {
           j->stale_wins++;
         }
       }
-      again = !over(*j, sh) && g_pool.running && !j->todo[k].empty();
+      again = !over(*j, sh) && g_pool.running && !j->dev[k].todo.empty();
     }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     const uint64_t hashed = sh.hashed.load();
@@ -255,10 +256,7 @@ void cpu_worker_run(Device& d) {
     // re-validated like a GPU winner (the same function: a hit is valid by construction)
     if (hit && host_work_value(j->pre.m, hn) == hv && hv >= j->threshold.load(std::memory_order_relaxed) &&
         j->status == kPending) {
-      decide_locked(*j, NPOW_OK, hn, hv);
-      j->t_decide = now_us();
-      j->winner_k = (int)k;
-      stop_other_devices_locked(*j, k);
+      accept_win(*j, k, hn, hv, 0.0, 0);  // (no win record: no time of its reading, no GPU timestamp)
     } else if (!j->decided && j->cancel_seen()) {
       j->cancel_req = true;
       decide_locked(*j, NPOW_CANCELLED);

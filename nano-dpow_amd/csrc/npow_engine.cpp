@@ -549,7 +549,7 @@ static double worker_cpu_ms(Device& d) {
   return ms;
 }
 
-// A job that finished early (npow_pool.cpp early_finish) returns before the launch that held it
+// A job that finished early (npow_pool.cpp Worker::early_finish) returns before the launch that held it
 // is retired and counted; with no slot left searching, that launch ends within a hash, so the
 // stats calls wait (bounded) until the worker has retired everything and the counters are whole.
 static void settle_stats(const Device& d) {

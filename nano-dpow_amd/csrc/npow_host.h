@@ -1,5 +1,5 @@
 // npow_host.h -- host-side state shared by the engine (npow_engine.cpp: devices, sweeps,
-// values, C ABI) and the work pool (npow_pool.cpp: concurrent first-win searches).
+// values, C ABI) and the work pool (npow_pool*.cpp: concurrent first-win searches).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <pthread.h>
@@ -62,7 +62,7 @@ struct Device {
   // statistics
   std::mutex stats_mu;
   uint64_t launches = 0, nonces = 0, invalid = 0;
-  uint64_t early = 0, early_mismatch = 0;  // jobs finished from a published final count (npow_pool.cpp)
+  uint64_t early = 0, early_mismatch = 0;  // jobs finished from a published final count (Worker::early_finish)
   uint64_t yields = 0, dyn = 0;            // launches yielded / jobs that joined a running launch
   uint64_t linger_ends = 0;                // lingering launches ended early (Worker::end_linger)
   uint64_t promotions = 0;                 // promotions published into a running counted launch (pool_promote)
@@ -78,7 +78,7 @@ struct Device {
   uint64_t linger_relays = 0;              // final counts that followed a kill relayed by a lingering workgroup
   double linger_ms = 0.0;                  // host-timed waits of lingering launches with nothing to hash (in kernel_ms)
   double idle_ms = 0.0;                    // GPU idle between consecutive search launches (HIP events) ...
-  uint64_t idle_gaps = 0;                  // ... over this many pairs (npow_pool.cpp Worker::retire)
+  uint64_t idle_gaps = 0;                  // ... over this many pairs (Worker::retire_launches)
   // Published by the pool worker for npow_device_stats_get: it has launches or slots in flight, and
   // how many of its slots are still searching.  A job finished early returns before the launch that
   // held it is retired; with no slot searching, the stats wait for the worker to retire the rest.
@@ -90,7 +90,7 @@ struct Device {
   std::mutex wake_mu;
   std::condition_variable wake_cv;
   uint64_t wake_seq = 0;
-  // The win watcher (npow_pool.cpp watcher_run): the slots whose win records it watches, armed by the pool worker
+  // The win watcher (npow_pool_watch.cpp watcher_run): the slots whose win records it watches, armed by the pool worker
   // when it adopts a job (bit s of armed_mask, the generation in armed_gen[s], the job in armed_job[s] under
   // armed_mu) and disarmed when the slot is freed.
   std::atomic<uint64_t> armed_mask{0};
@@ -170,7 +170,7 @@ std::vector<Device*> select_gpus(uint64_t mask);
 // Per-launch event accounting (kernel time by HIP events on the launch's own stream).
 void account_launch(Device& d, int ring);
 
-// ---- work pool (npow_pool.cpp) ----------------------------------------------------------------
+// ---- work pool (npow_pool.cpp; npow_pool_watch.cpp: its win watcher) ------------------------------------
 bool test_hooks_enabled();          // NANOPOW_TEST_HOOKS=1: the NANOPOW_FAULT_* hooks are honoured
 
 // Device affinity.  Every logical device runs on HIP device hip_id, and its HIP calls must come

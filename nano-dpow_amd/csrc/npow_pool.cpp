@@ -14,9 +14,13 @@
 // kMaxSlots roots live in every launch, so a root that is won mid-launch costs nothing:
 // its workgroups move on to the other live roots (npow_kernel.hip, pool_body_ls2).
 //
+// This file: the pool, its jobs and their transitions, a GPU's Worker, and the calls behind the C ABI.
+// npow_pool_watch.cpp: the win watcher; npow_cpu.cpp: the CPU device; npow_pool_impl.h: what the pool's files
+// share, the host's writes to a device's pinned mailbox among it (mb_kill, mb_boost, mb_floor, mb_yield).
+//
 // A job also leaves its launch early in both directions:
 // a won or killed job finishes from the final nonce count the kernel publishes once no workgroup is
-// left on its entry (early_finish; PoolMailbox::fin), and a new unbounded job joins the running
+// left on its entry (Worker::early_finish; PoolMailbox::fin), and a new unbounded job joins the running
 // launch as a dynamic entry (dyn_add; PoolMailbox::dyn) instead of ending it (yield_if_long, now
 // the fallback).  DESIGN.md section 1.
 //
@@ -42,24 +46,17 @@
 // (npow_engine.cpp: NANOPOW_FAULT_INIT=d fails npow_init on d.)
 #include <hip/hip_runtime.h>
 #include <sys/prctl.h>
-#include <time.h>
 
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <deque>
-#include <memory>
-#include <pthread.h>
 #include <mutex>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
-#include "npow_pool.h"
+#include "npow_pool_impl.h"
 
 namespace npow {
 namespace {
@@ -76,68 +73,15 @@ constexpr double kDynMinUs = 3000.0;     // join a running launch only with this
 constexpr double kFreshSpinUs = 400.0;   // poll without sleeping this long after a launch starts (quick wins)
 constexpr int kInvalidStreakMax = 3;     // consecutive invalid results that drop a device (@1669144)
 constexpr double kStopSpinUs = 2000.0;   // nap(): poll without sleeping this long after a slot's job stopped
-// Between steps a worker with a launch in flight sleeps this long (wakes early on new jobs):
-// a win is seen within it, and the thread costs ~6 % of a core instead of spinning (nap()).
-// NANOPOW_POLL_US overrides (0 = spin).
-const double g_poll_us = [] {
-  const char* e = getenv("NANOPOW_POLL_US");
-  return e ? atof(e) : 50.0;
-}();
-const bool g_debug = getenv("NANOPOW_DEBUG") != nullptr;
-// Lingering launches (round 5, PoolTable::linger): an unbounded launch's workgroups wait in it for the next dynamic
-// entry once its entries are over, so a serial client's next search joins the running launch instead of needing one.
-// The worker ends a launch that has lingered g_linger_us with nothing to do (end_linger): its sleeping waves hold the
-// CUs, and a serial client's next search comes within ~0.1 ms.  Measured on the 2^26-nonce regime, interleaved with
-// the same roots (profiles/r05aj_linger_by_partition_regime_ab.jsonl): over 8 CU partitions of 32
-// CUs the node rate goes 0.956 -> 0.98-0.99 of the devices' full rate with the p50 within +-0.05 ms; over 4, 2 and 1
-// (64 CUs and more) it costs -- node rate 0.97-0.995 against 0.996-1.0, p50 0.04-0.19 ms later -- since each
-// workgroup's acquire of a new entry (an L2 invalidation each) spreads their start, the more the more workgroups share
-// an XCD.  So by default on only for CU partitions of at most kLingerMaxCus CUs (lingers(); a whole GPU, and so every
-// physical GPU of a node, launches per search); NANOPOW_LINGER=1 / 0 forces it on / off, NANOPOW_LINGER_US sets the
-// wait.  Never for logical devices that time-share a GPU (Device::time_shared).
-const int g_linger_env = [] {
-  const char* e = getenv("NANOPOW_LINGER");
-  return e ? (e[0] == '0' ? 0 : 1) : -1;
-}();
-constexpr int kLingerMaxCus = 32;
-static bool lingers(const Device& d) {
-  if (d.time_shared) return false;
-  return g_linger_env >= 0 ? g_linger_env == 1 : (d.cu_first >= 0 && d.cus <= kLingerMaxCus);
-}
-const uint32_t g_linger_p = [] {  // NANOPOW_LINGER_P (A/B runs): the pinned-read period in looks (a power of two)
-  const char* e = getenv("NANOPOW_LINGER_P");
-  uint32_t p = e ? (uint32_t)atoi(e) : 0u, q = 1;
-  while (p && q < p) q <<= 1;
-  return p ? q : 0u;
-}();
-const double g_linger_us = [] {
-  const char* e = getenv("NANOPOW_LINGER_US");
-  return e ? atof(e) : 1000.0;
-}();
 // A slot whose job finished from its published final count is freed without reading its done counts back once the
 // launches that held it have completed, except every kVerifyEvery-th, which still checks the count against the
 // read-back (npow_device_stats.early_mismatches).  NANOPOW_READBACK=always reads every slot back (A/B runs).
 constexpr uint64_t kVerifyEvery = 16;
-const bool g_readback_always = [] {
-  const char* e = getenv("NANOPOW_READBACK");
-  return e && strcmp(e, "always") == 0;
-}();
-// The win watcher (watcher_run): on by default; NANOPOW_WATCHER=0 turns it off (A/B runs)
-const bool g_watcher_on = [] {
-  const char* e = getenv("NANOPOW_WATCHER");
-  return !(e && strcmp(e, "0") == 0);
-}();
-const bool g_trace_lat = getenv("NANOPOW_TRACE_LATENCY") != nullptr;
-// NANOPOW_TRACE_STEPS=1: each pool worker times the parts of its steps (adopt, check_slots, read-back, launch, retire,
-// nap) and prints count / total / max / calls over 50 us per part when it exits (diagnostics of the host path)
-const bool g_trace_steps = getenv("NANOPOW_TRACE_STEPS") != nullptr;
-// Fault injection (tests): see the header comment.
-struct Faults {
-  uint64_t invalid_mask = 0;  // logical devices whose wins read back corrupted
-  int hip_dev = -1;           // logical device whose launches fail ...
-  uint64_t hip_after = 0;     // ... after this many
-  bool retarget_blind = false;  // pool_retarget writes no floor record
-};
+constexpr int kLingerMaxCus = 32;  // lingering launches by default (npow_pool_impl.h g_linger_env)
+bool lingers(const Device& d) {
+  if (d.time_shared) return false;
+  return g_linger_env >= 0 ? g_linger_env == 1 : (d.cu_first >= 0 && d.cus <= kLingerMaxCus);
+}
 }  // namespace
 bool test_hooks_enabled() {
   static const bool on = [] {
@@ -146,7 +90,6 @@ bool test_hooks_enabled() {
   }();
   return on;
 }
-namespace {
 const Faults& faults() {
   static const Faults f = [] {
     Faults x;
@@ -179,39 +122,11 @@ const Faults& faults() {
   return f;
 }
 
-#define NPOW_DBG(...)                     \
-  do {                                    \
-    if (g_debug) fprintf(stderr, __VA_ARGS__); \
-  } while (0)
-// the same with the steady clock's time first (ms; Python's time.monotonic() * 1e3 reads the same clock)
-#define NPOW_DBGT(...)                                        \
-  do {                                                        \
-    if (g_debug) {                                            \
-      fprintf(stderr, "[%.3f] ", now_us() * 1e-3);            \
-      fprintf(stderr, __VA_ARGS__);                           \
-    }                                                         \
-  } while (0)
-
-}  // namespace
-
 // -- jobs shared with the CPU workers (npow_pool.h) ---------------------------------------------
-double now_us() {
-  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 Pool g_pool;
 std::atomic<uint64_t> g_gen{0};
 std::atomic<bool> g_exiting{false};
 std::atomic<double> g_exit_deadline_us{0.0};
-
-bool exit_now() {
-  if (g_exiting.load(std::memory_order_relaxed)) return true;
-  const double d = g_exit_deadline_us.load(std::memory_order_relaxed);
-  if (d > 0 && now_us() > d) {
-    g_exiting.store(true);
-    return true;
-  }
-  return false;
-}
 
 // -- deferred notifications (PoolLock, npow_pool.h) ----------------------------------------------
 namespace {
@@ -229,16 +144,17 @@ void notify_waiters_now(Job& j) {
 
 void notify_workers_now() {
   g_pool.cv_work.notify_all();
-  for (auto& dp : g_devs) {
-    Device& d = *dp;
-    {
-      std::lock_guard<std::mutex> g(d.wake_mu);
-      ++d.wake_seq;
-    }
-    d.wake_cv.notify_one();
-  }
+  for (auto& dp : g_devs) wake_worker(*dp);
 }
 }  // namespace
+
+void wake_worker(Device& d) {
+  {
+    std::lock_guard<std::mutex> g(d.wake_mu);
+    ++d.wake_seq;
+  }
+  d.wake_cv.notify_one();
+}
 
 PoolLock::PoolLock() : lk_(g_pool.mu) { t_defer.depth++; }
 
@@ -315,20 +231,21 @@ void finish_locked(const JobP& j) {
 
 // Device k of job j is finished with it (retired, exhausted, or the device failed).
 void device_done_locked(const JobP& j, size_t k, double t_seen) {
-  if (j->dev_done[k]) return;
-  j->dev_done[k] = 1;
-  j->on_dev[k] = 0;
-  if (j->seen_dev[k] && j->t_stop[k] == 0) j->t_stop[k] = t_seen > 0 ? t_seen : now_us();
+  JobDev& jd = j->dev[k];
+  if (jd.done) return;
+  jd.done = true;
+  jd.on = false;
+  if (jd.seen && jd.t_stop == 0) jd.t_stop = t_seen > 0 ? t_seen : now_us();
   if (--j->pending_devs == 0) finish_locked(j);
 }
 
-// Device k of job j is dead: hand the ranges it had not finished (j->todo[k], including any a
+// Device k of job j is dead: hand the ranges it had not finished (its todo, including any a
 // failed launch pushed back) to the job's surviving devices, split evenly (re-striding), then
 // release it.  With no survivor the job has lost part of its nonce space and fails.
 void abandon_locked(const JobP& j, size_t k, int code, const std::string& msg) {
-  if (j->dev_done[k]) return;
+  if (j->dev[k].done) return;
   std::deque<Range> rest;
-  rest.swap(j->todo[k]);
+  rest.swap(j->dev[k].todo);
   if (!j->decided && !rest.empty()) {
     // the surviving GPUs take it; the CPU device (npow_cpu.cpp) only when no GPU of the job is left
     std::vector<size_t> surv, surv_cpu;
@@ -347,13 +264,13 @@ void abandon_locked(const JobP& j, size_t k, int code, const std::string& msg) {
         uint64_t off = 0;
         for (uint64_t i = 0; i < S; ++i) {
           const uint64_t part = r.count / S + (i < r.count % S ? 1 : 0);
-          if (part) j->todo[surv[i]].push_back({r.base + off, part});
+          if (part) j->dev[surv[i]].todo.push_back({r.base + off, part});
           off += part;
         }
       }
       for (size_t k2 : surv)
-        if (j->dev_done[k2] && !j->todo[k2].empty()) {  // it had finished its own part: reopen
-          j->dev_done[k2] = 0;
+        if (j->dev[k2].done && !j->dev[k2].todo.empty()) {  // it had finished its own part: reopen
+          j->dev[k2].done = false;
           ++j->pending_devs;
         }
       g_pool.version.fetch_add(1);
@@ -365,248 +282,52 @@ void abandon_locked(const JobP& j, size_t k, int code, const std::string& msg) {
 
 // Job j has just been decided by device k_win's result: raise the kill word of every other device
 // that holds it now, instead of waiting for that device's worker to notice the decision at its next
-// step (it naps up to g_poll_us between steps), and wake the napping workers.  Each slot's kill
-// word is the job's generation there; a slot reused later has a larger generation, so a late store
-// could not stop another job -- and cannot happen anyway: a device releases a slot only under
-// g_pool.mu, after device_done_locked or a re-arm cleared on_dev.
+// step (it naps up to g_poll_us between steps), and wake the napping workers.  A late store could not
+// stop another job (mb_kill) -- and cannot happen anyway: a device releases a slot only under
+// g_pool.mu, after device_done_locked or a re-arm cleared JobDev::on.
 void stop_other_devices_locked(Job& j, size_t k_win) {
   if (j.devs.size() < 2) return;
-  for (size_t k = 0; k < j.devs.size(); ++k) {
-    if (k == k_win || !j.on_dev[k] || j.dev_slot[k] < 0) continue;  // (a CPU device has no slot: its threads
-                                                                      // read the decision themselves)
-    Device& d = *g_devs[(size_t)j.devs[k]];
-    __atomic_store_n(&d.pmb->kill[j.dev_slot[k]], j.dev_gen[k], __ATOMIC_RELEASE);
-    __atomic_fetch_add(&d.pmb->kills, 1ull, __ATOMIC_RELEASE);  // after the kill word: every poll then relays it
+  for_each_gpu_slot(j, [&](size_t k, Device& d, JobDev& jd) {
+    if (k == k_win) return;
+    mb_kill(d, jd.slot, jd.gen);
     std::lock_guard<std::mutex> sg(d.stats_mu);
     d.kills_relayed++;
-  }
+  });
   g_pool.decisions.fetch_add(1, std::memory_order_release);
   notify_workers_locked();
 }
 
-int index_in(const Job& j, int dev) {
-  for (size_t k = 0; k < j.devs.size(); ++k)
-    if (j.devs[k] == dev) return (int)k;
-  return -1;
+void accept_win(Job& j, size_t k, uint64_t nonce, uint64_t value, double t_seen, uint64_t gpu_t) {
+  decide_locked(j, NPOW_OK, nonce, value);
+  j.t_decide = now_us();
+  if (t_seen > 0) {
+    j.t_win_seen = t_seen;
+    if (j.t_win == 0) j.t_win = t_seen;
+  }
+  j.gpu_t_win = gpu_t;
+  j.winner_k = (int)k;
+  stop_other_devices_locked(j, k);
 }
 
 // Needs (under g_pool.mu): some active job wants this device.
 bool wants_device_locked(int dev) {
   for (const JobP& j : g_pool.active) {
     const int k = index_in(*j, dev);
-    if (k >= 0 && !j->on_dev[k] && !j->dev_done[k]) return true;
+    if (k >= 0 && !j->dev[k].on && !j->dev[k].done) return true;
   }
   return false;
 }
-
-// -- the win watcher ------------------------------------------------------------------------------
-// A device's pool worker sees its winner records only between its naps (up to g_poll_us = 50 us once a launch is
-// 0.4 ms old), and over 8 devices a worker woken by a notify queues for the pool lock behind the others.  One thread
-// for the whole process instead spins over the win records of every armed slot of every GPU while any job is live
-// (one core; it reads pinned host memory only, no HIP call), re-validates a winner on the CPU and decides the job
-// at once: the result goes to the client and the other devices' kill words go up within microseconds of the
-// record landing.  The winner's worker handles the same record at its next step as before (an invalid result, the
-// device's invalid streak and the slot's retirement stay its business; a job already decided is left alone).
-// It also watches each armed job's cancel word (a caller's work_cancel, or another rank's first win through a shared
-// word, bench.py node_time_to_work) and wakes the device's worker at once, which then stops the job's waves.
-// Spinning is bounded (round 6): the watcher spins while a job armed on a slot is within its spin window
-// -- three times the job's expected time to a win at its devices' rate (a win comes in it with probability 0.95),
-// at least kWatchSpinUs, at most kWatchSpinMaxUs; kWatchSpinUs only when a CPU device's hashing threads share the host
-// (--cpu-threads) -- or within kWatchSpinUs of a record it handled, and otherwise naps g_watch_nap_us at a time (1-us
-// timer slack).  So an endless or very hard search, or an idle lingering launch, costs a fraction of a core instead of
-// all of it, while a search of the expected length (the serial client's, 2-15 ms at fffffff8 on 8 GPUs or on one)
-// is watched spinning: a flat 2-ms window had put the nap's delay (~10-15 us) on every search longer than 2 ms -- the
-// 8-GPU time regime's fixed cost per search 6 -> 16 us on one GPU (profiles/r06f_regime1.json).
-// NANOPOW_WATCH_NAP_US=0 spins always.
-namespace {
-constexpr double kWatchSpinUs = 2000.0;
-constexpr double kWatchSpinMaxUs = 50000.0;
-constexpr double kNoncesPerCuUs = 139.0;  // a CU's search rate (35.6 Gnonce/s over 256 CUs)
-const double g_watch_nap_us = [] {
-  const char* e = getenv("NANOPOW_WATCH_NAP_US");
-  return e ? atof(e) : 20.0;
-}();
-struct Watch {
-  std::mutex mu;
-  std::condition_variable cv;
-  std::atomic<int> armed{0};        // armed slots over all devices
-  std::atomic<uint64_t> arms{0};    // arms so far (a new one restarts the spin window)
-  bool stop = false;
-  std::thread th;
-};
-Watch g_watch;
-}  // namespace
-
-// The slot's spin window (above): 3 x the job's expected nonces to a win / its GPU devices' rate, in [2, 50] ms.
-static double spin_window_us(const Job& j) {
-  bool cpu_device = false;
-  double rate = 0.0;  // nonces per us
-  for (const auto& dp : g_devs) cpu_device = cpu_device || dp->cpu_threads > 0;
-  if (cpu_device) return kWatchSpinUs;
-  for (int id : j.devs) {
-    const Device& d = *g_devs[(size_t)id];
-    if (!d.cpu_threads) rate += d.cus * kNoncesPerCuUs;
-  }
-  const double expect = 18446744073709551616.0 / (18446744073709551616.0 - (double)j.threshold.load() + 1.0);
-  const double w = rate > 0 ? 3.0 * expect / rate : kWatchSpinMaxUs;
-  return std::min(kWatchSpinMaxUs, std::max(kWatchSpinUs, w));
-}
-
-void watch_arm(Device& d, int s, uint64_t gen, const JobP& j) {
-  if (!g_watcher_on) return;
-  d.armed_spin_until[s].store(now_us() + j->spin_us, std::memory_order_relaxed);
-  {
-    std::lock_guard<std::mutex> g(d.armed_mu);
-    d.armed_job[s] = j;
-  }
-  d.armed_cancel[s].store(j->cancel, std::memory_order_release);
-  d.armed_gen[s].store(gen, std::memory_order_release);
-  const uint64_t bit = 1ull << s;
-  g_watch.arms.fetch_add(1, std::memory_order_acq_rel);  // (a napping watcher sees it within its nap: no wake-up here,
-                                                         // under the pool lock; a win comes ~0.2 ms after an arm at best)
-  if (!(d.armed_mask.fetch_or(bit, std::memory_order_acq_rel) & bit) &&
-      g_watch.armed.fetch_add(1, std::memory_order_acq_rel) == 0) {
-    { std::lock_guard<std::mutex> g(g_watch.mu); }
-    g_watch.cv.notify_one();
-  }
-}
-
-void watch_disarm(Device& d, int s) {
-  if (!g_watcher_on) return;
-  const uint64_t bit = 1ull << s;
-  if (d.armed_mask.fetch_and(~bit, std::memory_order_acq_rel) & bit) g_watch.armed.fetch_sub(1, std::memory_order_acq_rel);
-  std::lock_guard<std::mutex> g(d.armed_mu);  // (see watch_stop_cancel)
-  d.armed_gen[s].store(0, std::memory_order_release);
-  d.armed_cancel[s].store(nullptr, std::memory_order_release);
-  d.armed_job[s].reset();
-}
-
-// The slot leaves the searching state: the watcher stops reading its job's cancel word.  Under armed_mu, which the
-// watcher holds while it reads the word: the device cannot finish with the job before this, so the job cannot end and
-// its caller free the word while the watcher reads it.
-void watch_stop_cancel(Device& d, int s) {
-  if (!g_watcher_on) return;
-  std::lock_guard<std::mutex> g(d.armed_mu);
-  d.armed_cancel[s].store(nullptr, std::memory_order_release);
-}
-
-static void wake_worker(Device& d) {
-  {
-    std::lock_guard<std::mutex> g(d.wake_mu);
-    ++d.wake_seq;
-  }
-  d.wake_cv.notify_one();
-}
-
-namespace {
-void watch_handle(Device& d, int s, uint64_t gen) {
-  const double t_seen = now_us();
-  JobP j;
-  {
-    std::lock_guard<std::mutex> g(d.armed_mu);
-    if (d.armed_gen[s].load(std::memory_order_acquire) == gen) j = std::static_pointer_cast<Job>(d.armed_job[s]);
-  }
-  if (!j) return;
-  const PoolWin& pw = d.pmb->win[s];
-  const uint64_t n = __atomic_load_n(&pw.nonce, __ATOMIC_RELAXED);
-  uint64_t v = __atomic_load_n(&pw.value, __ATOMIC_RELAXED);
-  if (__atomic_load_n(&pw.gen, __ATOMIC_ACQUIRE) != gen) return;  // the record moved on meanwhile
-  if ((faults().invalid_mask >> d.id) & 1) v ^= 1;                 // NANOPOW_FAULT_INVALID (tests)
-  if (host_work_value(j->pre.m, n) != v || v < j->threshold.load(std::memory_order_relaxed))
-    return;  // invalid, or below a raised threshold (npow_retarget): the worker's business
-  PoolLock g;  // (j, a local reference, outlives it)
-  const int k = index_in(*j, d.id);
-  if (j->status != kPending || k < 0 || j->dev_gen[(size_t)k] != gen) return;
-  if (v < j->threshold.load(std::memory_order_relaxed)) return;  // raised since the look above (pool_retarget holds
-                                                                 // this lock): a decision never undercuts a raise
-  decide_locked(*j, NPOW_OK, n, v);
-  j->t_decide = now_us();
-  j->t_win_seen = t_seen;
-  j->gpu_t_win = __atomic_load_n(&pw.t, __ATOMIC_RELAXED);
-  if (j->t_win == 0) j->t_win = t_seen;
-  j->winner_k = k;
-  stop_other_devices_locked(*j, (size_t)k);
-  if (j->devs.size() < 2) notify_workers_locked();  // (stop_other_devices_locked wakes them for split jobs)
-  std::lock_guard<std::mutex> sg(d.stats_mu);
-  d.watcher_decisions++;
-}
-
-void watcher_run() {
-  prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);
-  std::vector<std::vector<uint64_t>> handled(g_devs.size(), std::vector<uint64_t>(kMaxSlots, 0));
-  std::vector<std::vector<uint64_t>> cancelled(g_devs.size(), std::vector<uint64_t>(kMaxSlots, 0));
-  uint64_t arms_seen = g_watch.arms.load(std::memory_order_acquire);
-  double t_event = now_us();  // the last arm or record change: spin until kWatchSpinUs after it
-  for (uint32_t round = 0;; ++round) {
-    if (g_watch.armed.load(std::memory_order_acquire) == 0) {
-      std::unique_lock<std::mutex> lk(g_watch.mu);
-      g_watch.cv.wait(lk, [] { return g_watch.stop || g_watch.armed.load(std::memory_order_acquire) > 0; });
-      if (g_watch.stop) return;
-      t_event = now_us();
-    }
-    if (exit_now()) return;
-    if ((round & 63u) == 0) {  // (the clock every 64 rounds: a round over a few armed slots is ~0.1 us)
-      const uint64_t a = g_watch.arms.load(std::memory_order_acquire);
-      const double t = now_us();
-      double until = t_event + kWatchSpinUs;  // the armed slots' spin windows (watch_arm)
-      for (const auto& dp : g_devs) {
-        for (uint64_t m = dp->armed_mask.load(std::memory_order_acquire); m; m &= m - 1)
-          until = std::max(until, dp->armed_spin_until[__builtin_ctzll(m)].load(std::memory_order_relaxed));
-      }
-      if (a != arms_seen) {
-        arms_seen = a;
-      } else if (g_watch_nap_us > 0 && t > until) {
-        std::unique_lock<std::mutex> lk(g_watch.mu);
-        g_watch.cv.wait_for(lk, std::chrono::duration<double, std::micro>(g_watch_nap_us), [&] {
-          return g_watch.stop || g_watch.arms.load(std::memory_order_acquire) != arms_seen;
-        });
-        if (g_watch.stop) return;
-      }
-    }
-    for (size_t di = 0; di < g_devs.size(); ++di) {
-      Device& d = *g_devs[di];
-      uint64_t m = d.armed_mask.load(std::memory_order_acquire);
-      while (m) {
-        const int s = __builtin_ctzll(m);
-        m &= m - 1;
-        const uint64_t gen = d.armed_gen[s].load(std::memory_order_acquire);
-        if (gen && gen != handled[di][s] && __atomic_load_n(&d.pmb->win[s].gen, __ATOMIC_ACQUIRE) == gen) {
-          handled[di][s] = gen;
-          watch_handle(d, s, gen);
-          t_event = now_us();
-        }
-        if (gen && gen != cancelled[di][s] && d.armed_cancel[s].load(std::memory_order_acquire)) {
-          bool raised;
-          {
-            std::lock_guard<std::mutex> g(d.armed_mu);  // (watch_stop_cancel)
-            const volatile uint32_t* c = d.armed_cancel[s].load(std::memory_order_acquire);
-            raised = c && load_acquire(c);
-          }
-          if (raised) {
-            cancelled[di][s] = gen;
-            wake_worker(d);  // its check_slots sees the cancel word and raises the slot's kill word
-          }
-        }
-      }
-    }
-    cpu_relax();
-  }
-}
-}  // namespace
 
 namespace {
 
 // -- one device's worker ------------------------------------------------------------------------
 enum class SlotState { kFree, kActive, kDraining };
 
-struct Slot {
-  SlotState state = SlotState::kFree;
+// What a slot knows of the job it holds: adopt() resets all of it with one assignment.
+struct Adoption {
   JobP job;
   size_t k = 0;            // the device's index within job->devs
   uint64_t gen = 0;
-  uint64_t baseline = 0;   // done counter of this slot index at its last retirement
-  uint64_t late_base = 0;  // ... and its late counter (kLateWord)
-  uint64_t stale_base = 0;  // ... and its stale-hit counter (kStaleWord)
   bool win_seen = false;
   bool requeue = false;    // invalid GPU result: hand the job back to this device after retiring
   bool no_more = false;    // bounded range fully issued
@@ -619,13 +340,21 @@ struct Slot {
   double stop_us = 0;      // the job was won or killed at this time: the worker polls without napping
                            // until the slot's final count is in (a quick return, and an exact stop time)
   bool stale = false;      // its final count had not come g_linger_us after stop_us (npow_device_stats.stale_drains)
-  struct Issued {
-    uint64_t seq, base, count;
-  };
+  struct Issued { uint64_t seq, base, count; };
   std::vector<Issued> inflight;  // ranges handed to launches that have not completed (in order)
   uint64_t unread = 0;           // bounded job: nonces of its completed ranges whose done shards have not
                                  // been read back (a failed device's fail_all counts them from this)
 };
+
+struct Slot : Adoption {
+  SlotState state = SlotState::kFree;
+  // The device's counters of this slot index only grow: what they read at the slot's last crediting (credit_counts)
+  uint64_t baseline = 0;    // done counter
+  uint64_t late_base = 0;   // late counter (kLateWord)
+  uint64_t stale_base = 0;  // stale-hit counter (kStaleWord)
+};
+
+struct Counts { uint64_t done, late, stale; };
 
 struct PoolInflight {
   uint64_t seq;
@@ -647,11 +376,10 @@ class Worker {
   Slot slots_[kMaxSlots];
   std::deque<PoolInflight> q_;
   uint64_t seq_ = 0;  // launches issued by this worker
-  uint64_t retired_seq_ = 0;  // the last launch retire() has dropped (launches retire in order)
+  uint64_t retired_seq_ = 0;  // the last launch retire_launches() has dropped (launches retire in order)
   uint64_t seen_version_ = ~0ull;
   int ring_ = 0;
   std::chrono::steady_clock::time_point front_start_{};  // host estimate of the running launch's start
-  uint64_t yields_ = 0;
   uint64_t ctl_ = 0;  // PoolMailbox::ctl (only this worker writes it): yields << 32 | dynamic entries
   uint64_t wake_seen_ = 0;  // Device::wake_seq as of this worker's last nap
   uint64_t early_count_ = 0;  // slots finished early so far (every kVerifyEvery-th is still read back)
@@ -688,23 +416,53 @@ class Worker {
   }
   std::unique_lock<std::mutex> dev_lock_{d_.mu, std::defer_lock};
 
+  template <class F>
+  void stat(F&& f) {  // the device's statistics (npow_device_stats_get reads them) change under their lock
+    std::lock_guard<std::mutex> sg(d_.stats_mu);
+    f();
+  }
+  void drop(int code, const std::string& msg) { d_.dead_code = code; d_.dead_msg = msg; d_.dead = true; }
   bool busy() const {
     if (!q_.empty()) return true;
     for (const Slot& s : slots_)
       if (s.state != SlotState::kFree) return true;
     return false;
   }
-  void adopt();
-  void yield_if_long();
-  bool dyn_add(int s);
-  bool live_slot() const {  // a slot some launch in flight (or a dynamic entry) is hashing
-    for (const Slot& sl : slots_)
-      if (sl.state == SlotState::kActive && !sl.fresh) return true;
+  bool live_slot(int except = -1) const {  // a slot (other than `except`) some launch in flight is hashing
+    for (int s = 0; s < kMaxSlots; ++s)
+      if (s != except && slots_[s].state == SlotState::kActive && !slots_[s].fresh) return true;
     return false;
   }
+  double budget_left_us() const {  // of the running launch's time budget, by the host's estimate of its start
+    return g_budget_us.load() -
+           std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - front_start_).count();
+  }
+  // Slot s stops searching: with `kill`, its waves are told so; the watcher stops reading its job's cancel word.
+  void stop_slot(int s, bool kill) {
+    if (kill) mb_kill(d_, s, slots_[s].gen);
+    slots_[s].state = SlotState::kDraining;
+    watch_stop_cancel(d_, s);
+  }
+  void free_slot(int s) {
+    watch_disarm(d_, s);
+    slots_[s].job.reset();
+    slots_[s].state = SlotState::kFree;
+  }
+  void adopt();
+  void yield_if_long();
+  void take_entry(Slot& sl, PoolEntry& pe, uint64_t want, uint64_t seq, double t);
+  bool dyn_add(int s);
   void end_linger();
   void handle_win(int s);
-  bool win_published(int s) const;
+  bool win_published(int s) const {
+    return !slots_[s].win_seen && __atomic_load_n(&d_.pmb->win[s].gen, __ATOMIC_ACQUIRE) == slots_[s].gen;
+  }
+  Counts credit_counts(Slot& sl, uint64_t total, uint64_t late, uint64_t stale);
+  static void credit_job_locked(const Slot& sl, const Counts& c) {
+    sl.job->done += c.done;
+    sl.job->dev[sl.k].late += c.late;
+    sl.job->stale_hits += c.stale;
+  }
   void early_finish(int s);
   // A stale slot's final count came after all (late): how late on the GPU's clock, after the job's deciding win at tw
   // (Job::gpu_t_win, read by the caller under g_pool.mu; npow_device_stats.stale_gpu_delay_us; one clock for CU
@@ -728,14 +486,23 @@ class Worker {
     d_.counted_inflight.store(c, std::memory_order_release);
   }
   void check_slots();
+  void build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded);
   int launch(bool empty_linger = false);
   int queue_readbacks();
-  int retire();
+  int retire_launches();
+  int retire_slots();
+  int retire() {
+    DEVCHECK(d_, "pool retire");
+    if (int rc = retire_launches()) return rc;
+    return retire_slots();
+  }
   void fail_all(const std::string& msg);
   uint64_t push_back_locked(Slot& sl, size_t from, bool skip_done = false);
   bool launch_completed(uint64_t seq) const;
-  bool launch_started(uint64_t seq) const;
   void account_clock(int ring, uint64_t seq, uint64_t* t0 = nullptr, uint64_t* t1 = nullptr);
+  void trace_fin(int s) const;
+  void trace_launch(const PoolInflight& f, uint64_t g0, uint64_t g1);
+  void trace_nofin(int s, uint64_t seq) const;
   int step();
   void nap();
 };
@@ -749,8 +516,9 @@ void Worker::adopt() {
   seen_version_ = g_pool.version.load();
   for (const JobP& j : std::vector<JobP>(g_pool.active)) {  // copy: device_done_locked may erase
     const int k = index_in(*j, d_.id);
-    if (k < 0 || j->on_dev[k] || j->dev_done[k]) continue;
-    if (j->decided || j->todo[k].empty()) {  // decided before this device got to it, or nothing left
+    if (k < 0 || j->dev[k].on || j->dev[k].done) continue;
+    JobDev& jd = j->dev[k];
+    if (j->decided || jd.todo.empty()) {  // decided before this device got to it, or nothing left
       device_done_locked(j, k);
       continue;
     }
@@ -761,24 +529,20 @@ void Worker::adopt() {
       break;
     }
     Slot& sl = slots_[s];
+    static_cast<Adoption&>(sl) = Adoption{};  // nothing of the slot's last job stays but the counters' baselines
     sl.state = SlotState::kActive;
     sl.job = j;
     sl.k = (size_t)k;
     sl.gen = ++g_gen;
-    sl.win_seen = sl.requeue = sl.no_more = sl.readback = sl.fin_seen = sl.early = sl.no_readback = false;
-    sl.stop_us = 0;
-    sl.stale = false;
-    sl.unread = 0;
     sl.fresh = true;
-    sl.inflight.clear();
-    j->on_dev[k] = 1;
-    j->dev_slot[k] = s;
-    j->dev_gen[k] = sl.gen;
+    jd.on = true;
+    jd.slot = s;
+    jd.gen = sl.gen;
     watch_arm(d_, s, sl.gen, j);
     if (j->t_adopt == 0) j->t_adopt = now_us();
-    sl.new_job = !j->seen_dev[k];
+    sl.new_job = !jd.seen;
     if (sl.new_job) adopted = true;  // a new job: worth ending a long launch for
-    j->seen_dev[k] = 1;
+    jd.seen = true;
   }
   // Unbounded jobs join the running launch as dynamic entries (no yield: the launch goes
   // on and workgroups move to them); a new job that cannot ends the long launch instead.
@@ -793,6 +557,32 @@ void Worker::adopt() {
   // spread over all of them at once, where one at a time they would crowd onto the first and rebalance slowly
   if (ctl_ != ctl0) __atomic_store_n(&d_.pmb->ctl, ctl_, __ATOMIC_RELEASE);
   if (adopted && waiting_new) yield_if_long();
+}
+
+// Fill entry pe (of launch seq's table, or a dynamic entry of it) from the job of slot sl: its uniforms, threshold,
+// generation and slot, and up to `want` nonces from the front of the device's queue of ranges, which then count as
+// handed to that launch.  The caller sets pe.bounded and pe.wsh, and holds g_pool.mu (the job's queue and timestamps
+// are shared with other workers).  t: now.
+void Worker::take_entry(Slot& sl, PoolEntry& pe, uint64_t want, uint64_t seq, double t) {
+  Job& j = *sl.job;
+  JobDev& jd = j.dev[sl.k];
+  memcpy(pe.u, j.u, sizeof(pe.u));
+  pe.threshold = j.threshold;
+  pe.gen = sl.gen;
+  pe.slot = (uint32_t)(&sl - slots_);
+  pe.pad = 0;
+  if (jd.todo.empty()) jd.todo.push_back({j.start, 0});  // cannot happen (adopt / no_more); an empty entry
+  Range& r = jd.todo.front();
+  pe.base = r.base;
+  pe.count = std::min(want, r.count);
+  r.base += pe.count;
+  r.count -= pe.count;
+  if (r.count == 0) jd.todo.pop_front();
+  sl.inflight.push_back({seq, pe.base, pe.count});
+  if (j.t_launch == 0) j.t_launch = t;
+  if (jd.t_launch == 0) jd.t_launch = t;
+  if (jd.todo.empty()) sl.no_more = true;
+  sl.fresh = false;
 }
 
 // Publish the job of fresh slot s as a dynamic entry of the running launch (npow_internal.h
@@ -817,60 +607,32 @@ bool Worker::dyn_add(int s) {
     // the ring holds both); it starts as soon as the other one's workgroups have left
     if (!f.linger || (uint32_t)(f.dyn_base - (uint32_t)q_.front().dyn_base) < (uint32_t)kDynEntries) return false;
   } else {
-    bool other = false;  // another live entry keeps the launch running (workgroups to move)
-    for (int k = 0; k < kMaxSlots && !other; ++k)
-      other = k != s && slots_[k].state == SlotState::kActive && !slots_[k].fresh;
-    if (!other && !f.linger) return false;  // they are leaving: the next launch, right after, takes the job
-    const double left_us = g_budget_us.load() - std::chrono::duration<double, std::micro>(
-                                                    std::chrono::steady_clock::now() - front_start_).count();
-    if (left_us < kDynMinUs) return false;  // the next launch, queued soon, takes it
+    // another live entry keeps the launch running (workgroups to move); else
+    if (!live_slot(s) && !f.linger) return false;  // they are leaving: the next launch, right after, takes the job
+    if (budget_left_us() < kDynMinUs) return false;  // the next launch, queued soon, takes it
   }
-  const uint32_t iters = sh.launch_iters(g_iters.load());
-  const uint64_t full = sh.full(iters);
-  std::deque<Range>& todo = j.todo[sl.k];
+  const uint64_t full = sh.full(sh.launch_iters(g_iters.load()));
+  const std::deque<Range>& todo = j.dev[sl.k].todo;
   if (todo.empty() || todo.front().count < full) return false;
   PoolEntry& pe = d_.pmb->dyn[(uint32_t)ctl_ % kDynRing].e;
-  memcpy(pe.u, j.u, sizeof(pe.u));
-  pe.threshold = j.threshold;
-  pe.gen = sl.gen;
-  pe.slot = (uint32_t)s;
+  take_entry(sl, pe, full, f.seq, now_us());
   pe.bounded = 0;
   // the scaled balancing rule (ls2_poll) moves workgroups here up to its weighted share; on the table's scale
   pe.wsh = pool_wsh((j.weight >> f.wdown) ? (j.weight >> f.wdown) : 1u);
-  pe.pad = 0;
-  Range& r = todo.front();
-  pe.base = r.base;
-  pe.count = full;
-  r.base += full;
-  r.count -= full;
-  if (r.count == 0) todo.pop_front();
-  sl.inflight.push_back({f.seq, pe.base, pe.count});
-  if (todo.empty()) sl.no_more = true;
-  sl.fresh = false;
-  {
-    const double t = now_us();
-    if (j.t_launch == 0) j.t_launch = t;
-    if (j.t_launch_dev[sl.k] == 0) j.t_launch_dev[sl.k] = t;
-  }
   ctl_ = (ctl_ & ~0xffffffffull) | (uint32_t)(ctl_ + 1);  // the low half wraps on its own (released by adopt())
-  {
-    std::lock_guard<std::mutex> sg(d_.stats_mu);
-    d_.dyn++;
-  }
+  stat([&] { d_.dyn++; });
   NPOW_DBGT("nanopow[%d]: dynamic entry %u: slot %d g%llu in launch %llu\n", d_.id, (uint32_t)ctl_ - 1u,
            s, (unsigned long long)sl.gen, (unsigned long long)f.seq);
   return true;
 }
 
-// New jobs wait for the next launch's table.  Launches run for a long time budget (their
-// start costs ~0.1-0.2 ms of cold instruction/scalar caches, so long launches are faster), so
-// when the running launch still has a while to go, end its unbounded entries now: bump the
-// pinned yield word (polling waves mark those entries dead) and hand their jobs back for
-// re-adoption with new generations next to the new ones.
+// New jobs wait for the next launch's table.  Launches run for a long time budget (their start costs ~0.1-0.2 ms of
+// cold instruction/scalar caches, so long launches are faster), so when the running launch still has a while to go, end
+// its unbounded entries now: a yield (polling waves mark those entries dead), and hand their jobs back for re-adoption
+// with new generations next to the new ones.
 void Worker::yield_if_long() {
   if (q_.empty() || g_budget_us.load() == 0) return;
-  const double left_us = g_budget_us.load() - std::chrono::duration<double, std::micro>(
-                                                  std::chrono::steady_clock::now() - front_start_).count();
+  const double left_us = budget_left_us();
   NPOW_DBG("nanopow[%d]: yield? inflight %zu left_us %.0f\n", d_.id, q_.size(), left_us);
   if (q_.size() < 2 && left_us < kYieldMinUs) return;
   int live = 0;
@@ -878,18 +640,16 @@ void Worker::yield_if_long() {
     if (sl.state == SlotState::kActive && !sl.fresh && !sl.job->max_per_dev) ++live;
   if (live >= kYieldMaxLive) return;
   bool any = false;
-  for (Slot& sl : slots_) {
+  for (int s = 0; s < kMaxSlots; ++s) {
+    Slot& sl = slots_[s];
     if (sl.state != SlotState::kActive || sl.fresh || sl.job->max_per_dev) continue;
     sl.requeue = true;
-    sl.state = SlotState::kDraining;
-    watch_stop_cancel(d_, (int)(&sl - slots_));
+    stop_slot(s, false);
     any = true;
   }
   NPOW_DBG("nanopow[%d]: yield %s\n", d_.id, any ? "raised" : "(no slot to hand back)");
   if (any) {
-    ctl_ += 1ull << 32;
-    __atomic_store_n(&d_.pmb->ctl, ctl_, __ATOMIC_RELEASE);
-    ++yields_;
+    mb_yield(d_, ctl_);
     std::lock_guard<std::mutex> sg(d_.stats_mu);
     d_.yields++;
   }
@@ -900,25 +660,16 @@ void Worker::handle_win(int s) {
   const double t_seen = now_us();
   Slot& sl = slots_[s];
   Job& j = *sl.job;
-  PoolWin& pw = d_.pmb->win[s];
   sl.win_seen = true;
-  const uint64_t n = __atomic_load_n(&pw.nonce, __ATOMIC_RELAXED);
-  uint64_t v = __atomic_load_n(&pw.value, __ATOMIC_RELAXED);
-  if ((faults().invalid_mask >> d_.id) & 1) v ^= 1;  // NANOPOW_FAULT_INVALID (tests)
+  uint64_t n, v;
+  read_win(d_, s, &n, &v);
   const uint64_t cpu_v = host_work_value(j.pre.m, n);
   PoolLock g;  // (the slot holds the job)
   if (j.t_win == 0) j.t_win = t_seen;
   const uint64_t threshold = j.threshold.load(std::memory_order_relaxed);  // (under the lock: pool_retarget)
   if (cpu_v == v && v >= threshold) {
     invalid_streak_ = 0;
-    if (j.status == kPending) {
-      decide_locked(j, NPOW_OK, n, v);
-      j.t_decide = now_us();
-      j.t_win_seen = t_seen;
-      j.gpu_t_win = __atomic_load_n(&pw.t, __ATOMIC_RELAXED);
-      j.winner_k = (int)sl.k;
-      stop_other_devices_locked(j, sl.k);
-    }
+    if (j.status == kPending) accept_win(j, sl.k, n, v, t_seen, __atomic_load_n(&d_.pmb->win[s].t, __ATOMIC_RELAXED));
   } else {
     // "GPU returned invalid work": the launches that held this generation stopped at the win,
     // so a bounded job gets back every range from the one holding the winner on; the job is
@@ -934,10 +685,7 @@ void Worker::handle_win(int s) {
       NPOW_DBGT("nanopow[%d]: slot %d g%llu: win %016llx below the raised threshold, re-armed\n", d_.id, s,
                 (unsigned long long)sl.gen, (unsigned long long)v);
     } else {
-      {
-        std::lock_guard<std::mutex> sg(d_.stats_mu);
-        d_.invalid++;
-      }
+      stat([&] { d_.invalid++; });
       fprintf(stderr, "nanopow: GPU %d returned invalid work %016llx (value %016llx, cpu %016llx)\n", d_.id,
               (unsigned long long)n, (unsigned long long)v, (unsigned long long)cpu_v);
     }
@@ -952,21 +700,18 @@ void Worker::handle_win(int s) {
     }
     sl.requeue = true;
     if (!stale && ++invalid_streak_ >= kInvalidStreakMax && !d_.dead) {
-      d_.dead_code = NPOW_ERR_INVALID_WORK;
-      d_.dead_msg = "GPU " + std::to_string(d_.id) + " returned invalid work " + std::to_string(kInvalidStreakMax) +
-                    " consecutive times";
-      d_.dead = true;
+      drop(NPOW_ERR_INVALID_WORK, "GPU " + std::to_string(d_.id) + " returned invalid work " +
+                                      std::to_string(kInvalidStreakMax) + " consecutive times");
       fprintf(stderr, "nanopow: %s, dropping it\n", d_.dead_msg.c_str());
     }
   }
-  sl.state = SlotState::kDraining;  // the winning wave already marked the slot dead on the device
-  watch_stop_cancel(d_, (int)(&sl - slots_));
+  stop_slot(s, false);  // the winning wave already marked the slot dead on the device
   sl.stop_us = now_us();
 }
 
 // Ranges sl.inflight[from..] did not complete (their launches stopped on this generation or
 // failed): hand them back to the front of the job's queue for this device, in order.  With
-// skip_done, a range whose launch has already completed on the GPU (retire() has not seen it yet)
+// skip_done, a range whose launch has already completed on the GPU (retire_launches() has not seen it yet)
 // stays: it was hashed in full, and handing it back would hash it again and over-count the job's
 // nonces_done (a dropped device's check_slots / fail_all).  Returns the nonces of the ranges kept.
 uint64_t Worker::push_back_locked(Slot& sl, size_t from, bool skip_done) {
@@ -980,25 +725,14 @@ uint64_t Worker::push_back_locked(Slot& sl, size_t from, bool skip_done) {
       kept += r.count;
       continue;
     }
-    j.todo[sl.k].push_front({r.base, r.count});
+    j.dev[sl.k].todo.push_front({r.base, r.count});
   }
   sl.inflight.swap(keep);
   return kept;
 }
 
-// The launch with sequence number seq has begun on the GPU: retired, or the start event recorded
-// right before it on the stream has fired (the launches ahead of it are done).
-bool Worker::launch_started(uint64_t seq) const {
-  if (seq <= retired_seq_) return true;
-  (void)check_device(d_, "launch_started");
-  for (const PoolInflight& f : q_)
-    if (f.seq == seq) return hipEventQuery(d_.ev_start[f.ring]) == hipSuccess;
-  return false;
-}
-
-// The launch with sequence number seq has completed on the GPU: retire() has dropped it, or its
-// stop event has fired.  A launch whose issue failed (its ranges were assigned, then the HIP call
-// failed: never in q_) has not.
+// The launch with sequence number seq has completed on the GPU: retire_launches() has dropped it, or its stop event has
+// fired.  A launch whose issue failed (its ranges were assigned, then the HIP call failed: never in q_) has not.
 bool Worker::launch_completed(uint64_t seq) const {
   if (seq <= retired_seq_) return true;
   (void)check_device(d_, "launch_completed");
@@ -1031,15 +765,52 @@ void Worker::account_clock(int ring, uint64_t seq, uint64_t* t0, uint64_t* t1) {
   d_.clk_ref_ticks += ref;
 }
 
-bool Worker::win_published(int s) const {
+// The device's counters of sl's slot index read total / late / stale now: credit what they gained since the slot's
+// last crediting to the device's statistics, move the baselines up, and return the gains for the job
+// (credit_job_locked, under g_pool.mu).
+Counts Worker::credit_counts(Slot& sl, uint64_t total, uint64_t late, uint64_t stale) {
+  const Counts c{total - sl.baseline, late - sl.late_base, stale - sl.stale_base};
+  sl.baseline = total;
+  sl.late_base = late;
+  sl.stale_base = stale;
+  std::lock_guard<std::mutex> sg(d_.stats_mu);
+  d_.nonces += c.done;
+  d_.late += c.late;
+  return c;
+}
+
+// NANOPOW_TRACE_LATENCY: the GPU timeline of slot s's final count (one GPU's clock: CU partitions), from the job's
+// deciding win.  Caller holds g_pool.mu.
+void Worker::trace_fin(int s) const {
   const Slot& sl = slots_[s];
-  return !sl.win_seen && __atomic_load_n(&d_.pmb->win[s].gen, __ATOMIC_ACQUIRE) == sl.gen;
+  const Job& j = *sl.job;
+  const double tw = (double)j.gpu_t_win, tr = (double)__atomic_load_n(&d_.pmb->fin[s].t_relay, __ATOMIC_RELAXED);
+  fprintf(stderr, "[%.3f] nanopow-fin dev %d ticket %llu: relay %+.1f fin %+.1f seen %+.1f us (host) from the win%s\n",
+          now_us() * 1e-3, d_.id, (unsigned long long)j.ticket, (tr - tw) / 100.0,
+          ((double)__atomic_load_n(&d_.pmb->fin[s].t_fin, __ATOMIC_RELAXED) - tw) / 100.0,
+          j.t_win_seen > 0 ? now_us() - j.t_win_seen : -1.0, (int)sl.k == j.winner_k ? " (winner)" : "");
+#ifdef NPOW_DIAG_TIMES
+    // absolute GPU times (100 MHz) of this entry's last start and its win, host times (us) of its launch / dynamic
+    // entry and of its win seen: a serial client's gap between one search's win and the next one's hashing
+  fprintf(stderr, "nanopow-join dev %d ticket %llu: gpu_join %llu gpu_win %llu host_launch %.1f host_win_seen %.1f\n",
+          d_.id, (unsigned long long)j.ticket,
+          (unsigned long long)__atomic_load_n(&d_.pmb->fin[s].t_join, __ATOMIC_RELAXED),
+          (unsigned long long)j.gpu_t_win, j.dev[sl.k].t_launch, j.t_win_seen);
+  // every workgroup's last entry start (a serial client: this search's) -- its spread
+  std::vector<uint64_t> tj;
+  const int G = ls_grid(d_) < 1024 ? ls_grid(d_) : 1024;
+  for (int g = 0; g < G; ++g) tj.push_back(__atomic_load_n(&d_.pmb->diag_join[g], __ATOMIC_RELAXED));
+  std::sort(tj.begin(), tj.end());
+  fprintf(stderr, "nanopow-joins dev %d ticket %llu: min %llu p10 %llu p50 %llu p90 %llu max %llu\n", d_.id,
+          (unsigned long long)j.ticket, (unsigned long long)tj[0], (unsigned long long)tj[G / 10],
+          (unsigned long long)tj[G / 2], (unsigned long long)tj[G * 9 / 10], (unsigned long long)tj[G - 1]);
+#endif
 }
 
 // The kernel published slot s's final nonce count (npow_kernel.hip "Early
 // finish"): no workgroup is on the entry and none can join it, so a decided job is finished now
 // instead of after the launch -- which its other entries may keep running for the rest of its
-// budget.  A yielded entry (the job is re-adopted) or an invalid win (re-armed) waits for retire().
+// budget.  A yielded entry (the job is re-adopted) or an invalid win (re-armed) waits for retire_slots().
 void Worker::early_finish(int s) {
   const double t_obs = now_us();  // the device's stop as this worker saw it (not when it got the pool lock)
   Slot& sl = slots_[s];
@@ -1050,54 +821,15 @@ void Worker::early_finish(int s) {
   const uint64_t stale_hits = __atomic_load_n(&d_.pmb->fin[s].stale, __ATOMIC_RELAXED);
   PoolLock g;  // (the slot holds the job)
   Job& j = *sl.job;
-  if (g_trace_lat && j.gpu_t_win) {  // GPU timeline (one GPU's clock: CU partitions), from the deciding win
-    const double tw = (double)j.gpu_t_win, tr = (double)__atomic_load_n(&d_.pmb->fin[s].t_relay, __ATOMIC_RELAXED);
-    fprintf(stderr, "[%.3f] nanopow-fin dev %d ticket %llu: relay %+.1f fin %+.1f seen %+.1f us (host) from the win%s\n",
-            now_us() * 1e-3, d_.id, (unsigned long long)j.ticket, (tr - tw) / 100.0,
-            ((double)__atomic_load_n(&d_.pmb->fin[s].t_fin, __ATOMIC_RELAXED) - tw) / 100.0,
-            j.t_win_seen > 0 ? now_us() - j.t_win_seen : -1.0, (int)sl.k == j.winner_k ? " (winner)" : "");
-#ifdef NPOW_DIAG_TIMES
-    // absolute GPU times (100 MHz) of this entry's last start and its win, host times (us) of its launch / dynamic
-    // entry and of its win seen: a serial client's gap between one search's win and the next one's hashing
-    fprintf(stderr, "nanopow-join dev %d ticket %llu: gpu_join %llu gpu_win %llu host_launch %.1f host_win_seen %.1f\n",
-            d_.id, (unsigned long long)j.ticket,
-            (unsigned long long)__atomic_load_n(&d_.pmb->fin[s].t_join, __ATOMIC_RELAXED),
-            (unsigned long long)j.gpu_t_win, j.t_launch_dev[sl.k], j.t_win_seen);
-    {  // every workgroup's last entry start (a serial client: this search's) -- its spread
-      std::vector<uint64_t> tj;
-      const int G = ls_grid(d_) < 1024 ? ls_grid(d_) : 1024;
-      for (int g = 0; g < G; ++g) tj.push_back(__atomic_load_n(&d_.pmb->diag_join[g], __ATOMIC_RELAXED));
-      std::sort(tj.begin(), tj.end());
-      fprintf(stderr, "nanopow-joins dev %d ticket %llu: min %llu p10 %llu p50 %llu p90 %llu max %llu\n", d_.id,
-              (unsigned long long)j.ticket, (unsigned long long)tj[0], (unsigned long long)tj[G / 10],
-              (unsigned long long)tj[G / 2], (unsigned long long)tj[G * 9 / 10], (unsigned long long)tj[G - 1]);
-    }
-#endif
-  }
-  if (__atomic_load_n(&d_.pmb->fin[s].linger_gen, __ATOMIC_RELAXED) == sl.gen) {  // relayed by a lingering workgroup
-    std::lock_guard<std::mutex> sg(d_.stats_mu);
-    d_.linger_relays++;
-  }
+  if (g_trace_lat && j.gpu_t_win) trace_fin(s);
+  if (__atomic_load_n(&d_.pmb->fin[s].linger_gen, __ATOMIC_RELAXED) == sl.gen)  // relayed by a lingering workgroup
+    stat([&] { d_.linger_relays++; });
   if (sl.stale) stale_fin_came(s, j.gpu_t_win);
   if (d_.dead || sl.requeue || !j.decided.load()) return;
   sl.early = true;
-  const uint64_t delta = total - sl.baseline;
-  sl.baseline = total;  // retire() then reads back the same total: a delta of 0
-  j.done += delta;
-  j.late[sl.k] += late - sl.late_base;
-  j.stale_hits += stale_hits - sl.stale_base;
-  {
-    std::lock_guard<std::mutex> sg(d_.stats_mu);
-    d_.late += late - sl.late_base;
-  }
-  sl.late_base = late;
-  sl.stale_base = stale_hits;
+  credit_job_locked(sl, credit_counts(sl, total, late, stale_hits));  // retire_slots() then reads back the same total
   if (g_trace_lat && j.t_kend == 0) j.t_kend = now_us();
-  {
-    std::lock_guard<std::mutex> sg(d_.stats_mu);
-    d_.nonces += delta;
-    d_.early++;
-  }
+  stat([&] { d_.early++; });
   device_done_locked(sl.job, sl.k, t_obs);
 }
 
@@ -1111,15 +843,12 @@ void Worker::check_slots() {
     }
     if (sl.state != SlotState::kActive) continue;
     Job& j = *sl.job;
-    if (d_.dead) {  // dropped device: stop every job's waves; retire() re-strides them
+    if (d_.dead) {  // dropped device: stop every job's waves; retire_slots() re-strides them
       if (j.max_per_dev) {  // the killed launches leave their ranges unfinished: hand them back
         std::lock_guard<std::mutex> g(g_pool.mu);
         push_back_locked(sl, 0, true);
       }
-      __atomic_store_n(&d_.pmb->kill[s], sl.gen, __ATOMIC_RELEASE);
-      __atomic_fetch_add(&d_.pmb->kills, 1ull, __ATOMIC_RELEASE);
-      sl.state = SlotState::kDraining;
-      watch_stop_cancel(d_, (int)(&sl - slots_));
+      stop_slot(s, true);
     } else if (j.decided.load(std::memory_order_relaxed) || j.cancel_seen()) {
       {
         PoolLock g;  // (the slot holds the job)
@@ -1128,20 +857,16 @@ void Worker::check_slots() {
           decide_locked(j, NPOW_CANCELLED);
         }
         // No launch holds the job on this device (adopted, waiting for the next launch's table): it hashes
-        // nothing more of it, from now.  Otherwise the stop time (Job::t_stop) is taken when this worker sees
-        // it stop hashing: its final count published, or the last launch that held it completed (retire()).
+        // nothing more of it, from now.  Otherwise the stop time (JobDev::t_stop) is taken when this worker sees
+        // it stop hashing: its final count published, or the last launch that held it completed (retire_launches()).
         // A launch queued behind another and started after the kill still hashes the job until one of its
         // waves polls the kill word (within an iteration), so "not started at the decision" is no proof of zero.
-        if (sl.inflight.empty() && j.t_stop[sl.k] == 0) j.t_stop[sl.k] = now_us();
+        if (sl.inflight.empty() && j.dev[sl.k].t_stop == 0) j.dev[sl.k].t_stop = now_us();
       }
-      __atomic_store_n(&d_.pmb->kill[s], sl.gen, __ATOMIC_RELEASE);  // in-flight waves stop
-      __atomic_fetch_add(&d_.pmb->kills, 1ull, __ATOMIC_RELEASE);
-      sl.state = SlotState::kDraining;
-      watch_stop_cancel(d_, (int)(&sl - slots_));
+      stop_slot(s, true);  // in-flight waves stop
       sl.stop_us = now_us();
     } else if (sl.no_more) {
-      sl.state = SlotState::kDraining;
-      watch_stop_cancel(d_, (int)(&sl - slots_));
+      stop_slot(s, false);
     }
   }
   publish_busy();  // before a job can finish early: its waiter may read the stats at once
@@ -1155,45 +880,25 @@ void Worker::check_slots() {
 
 // No live entry in the launches in flight, and something waits for the device (a job that could not join them, a
 // sweep / values task, shutdown, a dropped device): a lingering launch would hold the device until its budget ends
-// (up to 20 ms), so end it now -- a yield (the high half of PoolMailbox::ctl), which its lingering workgroups read
+// (up to 20 ms), so end it now -- a yield, which its lingering workgroups read
 // within a look (ls2_linger) and which ends nothing else, no entry being live.  Raised before the next table is built
 // (launch() takes yield_base after it), so that launch is not ended too.
 void Worker::end_linger() {
   bool lingering = false;
   for (const PoolInflight& f : q_) lingering = lingering || (f.linger && (f.yield_base >> 32) == (ctl_ >> 32));
   if (!lingering) return;
-  ctl_ += 1ull << 32;
-  __atomic_store_n(&d_.pmb->ctl, ctl_, __ATOMIC_RELEASE);
+  mb_yield(d_, ctl_);
   NPOW_DBGT("nanopow[%d]: lingering launch ended (ctl %llx)\n", d_.id, (unsigned long long)ctl_);
   std::lock_guard<std::mutex> sg(d_.stats_mu);
   d_.linger_ends++;
 }
 
-int Worker::launch(bool empty_linger) {
-  if (q_.size() >= 2 || d_.dead) return NPOW_OK;
-  // The second launch in flight only has to be queued before the running one ends (its budget
-  // is known): queued early, it would sit behind a launch that a win ends, and the job could
-  // only be retired after it too had started and drained (~20 us of every search's latency).
-  // ... unless no live entry is left in it (its jobs won or were killed: it ends within a hash, and a
-  // job finished early returns before that) -- then the next launch queues behind it at once.
-  if (q_.size() == 1 && g_budget_us.load() > 0 &&
-      std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - front_start_).count() <
-          (double)g_budget_us.load() - kPrelaunchUs) {
-    bool live = false;
-    for (int k = 0; k < kMaxSlots && !live; ++k) live = slots_[k].state == SlotState::kActive && !slots_[k].fresh;
-    if (live) return NPOW_OK;
-  }
+// The table of launch ++seq_ over the n slots idx[]: their entries (take_entry), the start map, the lingering mode.
+void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded) {
   const PoolShape sh = pool_shape(d_);
   const uint32_t iters = sh.launch_iters(g_iters.load());
-  PoolTable& t = *d_.h_tab[ring_];
-  uint32_t n = 0, wdown = 0;
+  uint32_t wdown = 0;
   uint32_t weights[kMaxSlots], wshs[kMaxSlots];
-  bool bounded = false;
-  int idx[kMaxSlots];
-  for (int s = 0; s < kMaxSlots; ++s)
-    if (slots_[s].state == SlotState::kActive && !slots_[s].no_more) idx[n++] = s;
-  if (n == 0 && !empty_linger) return NPOW_OK;
-  if (!live_slot()) end_linger();  // (step() has raised it already when a job waits; a bounded range's next part)
   t.n = n;
   t.poll_mask = poll_mask();
   t.iters = iters;
@@ -1216,41 +921,20 @@ int Worker::launch(bool empty_linger) {
     // promotion is either in the weights read below or bumps the counter past this base, which the kernel then sees
     t.promo_base = (uint32_t)(__atomic_load_n(&d_.pmb->kills, __ATOMIC_ACQUIRE) >> 32);
     const double t_issue = now_us();
+    const uint64_t full = sh.full(iters);
     for (uint32_t e = 0; e < n; ++e) {
       Slot& sl = slots_[idx[e]];
-      Job& j = *sl.job;
-      PoolEntry& pe = t.e[e];
-      memcpy(pe.u, j.u, sizeof(pe.u));
-      pe.threshold = j.threshold;
-      pe.gen = sl.gen;
-      pe.slot = (uint32_t)idx[e];
+      const Job& j = *sl.job;
+      const std::deque<Range>& todo = j.dev[sl.k].todo;
       // the next part of the device's queue of ranges: a bounded job's own waves cover it
       // densely; an unbounded job claims a full launch region (W * iters * 64, holes allowed)
       // unless less than that is left, which then becomes a dense bounded entry too
-      std::deque<Range>& todo = j.todo[sl.k];
-      const uint64_t own = sh.own(e, n, iters);
-      const uint64_t full = sh.full(iters);
-      if (todo.empty()) todo.push_back({j.start, 0});  // cannot happen (adopt / no_more); an empty entry
-      Range& r = todo.front();
-      const uint64_t want = j.max_per_dev ? own : full;
-      pe.base = r.base;
-      pe.count = std::min(want, r.count);
-      pe.bounded = (j.max_per_dev || pe.count < full) ? 1 : 0;
-      pe.wsh = pool_wsh(j.weight);
-      pe.pad = 0;
+      const bool dense = j.max_per_dev || todo.empty() || todo.front().count < full;
+      take_entry(sl, t.e[e], dense ? sh.own(e, n, iters) : full, seq_, t_issue);
+      t.e[e].bounded = dense ? 1 : 0;
+      t.e[e].wsh = pool_wsh(j.weight);
       weights[e] = j.weight;
-      if (pe.bounded) {
-        pe.count = std::min(pe.count, own);
-        bounded = true;
-      }
-      r.base += pe.count;
-      r.count -= pe.count;
-      if (r.count == 0) todo.pop_front();
-      sl.inflight.push_back({seq_, pe.base, pe.count});
-      if (j.t_launch == 0) j.t_launch = t_issue;
-      if (j.t_launch_dev[sl.k] == 0) j.t_launch_dev[sl.k] = t_issue;
-      if (todo.empty()) sl.no_more = true;
-      sl.fresh = false;
+      *bounded = *bounded || dense;
     }
   }
   // The start map (PoolTable::wsum): workgroup g starts on the entry whose run of the cumulative weights holds
@@ -1259,13 +943,13 @@ int Worker::launch(bool empty_linger) {
   // g % n == e): g % n.  Only differing weights need the map, and a workgroup must start on every entry, or that
   // entry would stay without one: pool_table_weights (npow_weights.h) halves a crowded table's weights until so.
   t.wsum = 0;
-  if (!bounded) {
+  if (!*bounded) {
     t.wsum = pool_table_weights(weights, n, (uint32_t)sh.grid, wshs, &wdown);
     for (uint32_t e = 0; e < n; ++e) t.e[e].wsh = wshs[e];
   }
   t.wdown = wdown;  // (a promoted weight is published raw: the kernel halves it as the table's were, pool_promoted_wsh)
   t.pad = 0;
-  if (lingers(d_) && !bounded && g_budget_us.load() > 0) {
+  if (lingers(d_) && !*bounded && g_budget_us.load() > 0) {
     // each lingering workgroup reads the pinned ctl word once in P looks (phase g): ~2 reads per look grid-wide
     uint32_t P = 1;
     while (P * 2 < (uint32_t)sh.grid) P <<= 1;
@@ -1273,7 +957,27 @@ int Worker::launch(bool empty_linger) {
     t.linger = P;
     t.counted = 1u;
   }
+}
+
+int Worker::launch(bool empty_linger) {
+  if (q_.size() >= 2 || d_.dead) return NPOW_OK;
+  // The second launch in flight only has to be queued before the running one ends (its budget
+  // is known): queued early, it would sit behind a launch that a win ends, and the job could
+  // only be retired after it too had started and drained (~20 us of every search's latency).
+  // ... unless no live entry is left in it (its jobs won or were killed: it ends within a hash, and a
+  // job finished early returns before that) -- then the next launch queues behind it at once.
+  if (q_.size() == 1 && g_budget_us.load() > 0 && budget_left_us() > kPrelaunchUs && live_slot()) return NPOW_OK;
+  uint32_t n = 0;
+  int idx[kMaxSlots];
+  for (int s = 0; s < kMaxSlots; ++s)
+    if (slots_[s].state == SlotState::kActive && !slots_[s].no_more) idx[n++] = s;
+  if (n == 0 && !empty_linger) return NPOW_OK;
+  if (!live_slot()) end_linger();  // (step() has raised it already when a job waits; a bounded range's next part)
+  PoolTable& t = *d_.h_tab[ring_];
+  bool bounded = false;
+  build_table(t, idx, n, &bounded);
   if (n == 0 && !t.linger) return NPOW_OK;
+  const PoolShape sh = pool_shape(d_);
   const int r = ring_;
   ring_ = (ring_ + 1) % kEventRing;
   const size_t bytes = pool_table_bytes(n);
@@ -1296,10 +1000,10 @@ int Worker::launch(bool empty_linger) {
   HIPTRY(hipEventRecord(d_.ev_stop[r], d_.stream));
   if (q_.empty()) front_start_ = std::chrono::steady_clock::now();
   NPOW_DBGT("nanopow[%d]: launch %llu n=%u linger %u wsum %u (weights halved %u times) yield_base %llx slots:", d_.id,
-            (unsigned long long)seq_, n, t.linger, t.wsum, wdown, (unsigned long long)t.yield_base);
+            (unsigned long long)seq_, n, t.linger, t.wsum, t.wdown, (unsigned long long)t.yield_base);
   for (uint32_t e = 0; e < n; ++e) NPOW_DBG(" %d/g%llu", idx[e], (unsigned long long)t.e[e].gen);
   NPOW_DBG("\n");
-  q_.push_back({seq_, r, (uint32_t)ctl_, t.yield_base, t.counted != 0, t.linger != 0, wdown});
+  q_.push_back({seq_, r, (uint32_t)ctl_, t.yield_base, t.counted != 0, t.linger != 0, t.wdown});
   publish_counted();
   return NPOW_OK;
 }
@@ -1327,7 +1031,7 @@ int Worker::queue_readbacks() {
                  now_us() - sl.stop_us < g_linger_us) {
         continue;  // won or killed: its final count is on the way (or its launches end without one) -- for
                    // g_linger_us at most: then the read-back is queued now, before the next launch is issued
-                   // (ADVICE r05), not behind it; a final count that still comes is checked against it (retire())
+                   // (ADVICE r05), not behind it; a final count that still comes is checked against it (retire_slots())
       }
     }
     HIPTRY(hipMemcpyAsync(d_.h_done + (size_t)s * row, &d_.pst->done[s][0], row * sizeof(unsigned long long),
@@ -1338,52 +1042,59 @@ int Worker::queue_readbacks() {
   return NPOW_OK;
 }
 
-int Worker::retire() {
-  DEVCHECK(d_, "pool retire");
+// NANOPOW_TRACE_LATENCY: retired launch f's event span against its clock waves' span g0..g1 (dispatch and drain), and
+// the GPU timeline of each decided job it held, from the deciding win (the same clock only for devices on one GPU: CU
+// partitions)
+void Worker::trace_launch(const PoolInflight& f, uint64_t g0, uint64_t g1) {
+  float ev = 0.f;
+  if (hipEventElapsedTime(&ev, d_.ev_start[f.ring], d_.ev_stop[f.ring]) == hipSuccess)
+    fprintf(stderr, "nanopow-launch dev %d launch %llu: events %.1f clock waves %.1f us, start %.1f us after the "
+            "previous end\n", d_.id, (unsigned long long)f.seq, ev * 1e3, (double)(g1 - g0) / 100.0,
+            prev_g1_ ? ((double)g0 - (double)prev_g1_) / 100.0 : -1.0);
+  prev_g1_ = g1;
+  for (const Slot& sl : slots_)
+    if (sl.state != SlotState::kFree && sl.job && sl.job->gpu_t_win && !sl.inflight.empty() &&
+        sl.inflight.front().seq <= f.seq)
+      fprintf(stderr, "nanopow-gpu dev %d ticket %llu launch %llu: start %+.1f end %+.1f us from the win\n", d_.id,
+              (unsigned long long)sl.job->ticket, (unsigned long long)f.seq,
+              ((double)g0 - (double)sl.job->gpu_t_win) / 100.0, ((double)g1 - (double)sl.job->gpu_t_win) / 100.0);
+}
+
+// NANOPOW_TRACE_LATENCY: slot s's decided job stopped on this device when launch seq ended, with no final count
+void Worker::trace_nofin(int s, uint64_t seq) const {
+  fprintf(stderr, "nanopow-nofin dev %d ticket %llu slot %d g%llu: stopped at its launch's end, no final "
+          "count (launch %llu, fin gen %llu)\n", d_.id, (unsigned long long)slots_[s].job->ticket, s,
+          (unsigned long long)slots_[s].gen, (unsigned long long)seq,
+          (unsigned long long)__atomic_load_n(&d_.pmb->fin[s].gen, __ATOMIC_ACQUIRE));
+}
+
+// The launches that have completed, in order: their statistics, and the ranges they held leave the slots' inflight.
+int Worker::retire_launches() {
   while (!q_.empty()) {
-    const hipError_t e = hipEventQuery(d_.ev_stop[q_.front().ring]);
+    const PoolInflight f = q_.front();
+    const hipError_t e = hipEventQuery(d_.ev_stop[f.ring]);
     if (e == hipErrorNotReady) break;
     if (e != hipSuccess) return fail(NPOW_ERR_HIP, std::string("pool launch: ") + hipGetErrorString(e));
-    account_launch(d_, q_.front().ring);
+    account_launch(d_, f.ring);
     // the GPU idle before this launch: the previous launch's stop event to this one's start event (the ring slot of
     // the previous launch is not reused before this one retires: at most two launches are in flight)
     if (prev_stop_ring_ >= 0) {
       float gap = 0.f;
-      if (hipEventElapsedTime(&gap, d_.ev_stop[prev_stop_ring_], d_.ev_start[q_.front().ring]) == hipSuccess &&
-          gap >= 0.f) {
-        std::lock_guard<std::mutex> sg(d_.stats_mu);
-        d_.idle_ms += gap;
-        d_.idle_gaps++;
-      }
+      if (hipEventElapsedTime(&gap, d_.ev_stop[prev_stop_ring_], d_.ev_start[f.ring]) == hipSuccess && gap >= 0.f)
+        stat([&] { d_.idle_ms += gap; d_.idle_gaps++; });
     }
-    prev_stop_ring_ = q_.front().ring;
+    prev_stop_ring_ = f.ring;
     uint64_t g0 = 0, g1 = 0;
-    account_clock(q_.front().ring, q_.front().seq, &g0, &g1);
-    if (g_trace_lat && g0) {  // the launch's event span against its clock waves' span (dispatch and drain)
-      float ev = 0.f;
-      if (hipEventElapsedTime(&ev, d_.ev_start[q_.front().ring], d_.ev_stop[q_.front().ring]) == hipSuccess)
-        fprintf(stderr, "nanopow-launch dev %d launch %llu: events %.1f clock waves %.1f us, start %.1f us after the "
-                "previous end\n", d_.id, (unsigned long long)q_.front().seq, ev * 1e3, (double)(g1 - g0) / 100.0,
-                prev_g1_ ? ((double)g0 - (double)prev_g1_) / 100.0 : -1.0);
-      prev_g1_ = g1;
-    }
-    if (g_trace_lat && g0)  // GPU timeline of a decided job's launch on this device, from the deciding win (the same
-                            // clock only for devices on one GPU: CU partitions)
-      for (const Slot& sl : slots_)
-        if (sl.state != SlotState::kFree && sl.job && sl.job->gpu_t_win && !sl.inflight.empty() &&
-            sl.inflight.front().seq <= q_.front().seq)
-          fprintf(stderr, "nanopow-gpu dev %d ticket %llu launch %llu: start %+.1f end %+.1f us from the win\n", d_.id,
-                  (unsigned long long)sl.job->ticket, (unsigned long long)q_.front().seq,
-                  ((double)g0 - (double)sl.job->gpu_t_win) / 100.0, ((double)g1 - (double)sl.job->gpu_t_win) / 100.0);
+    account_clock(f.ring, f.seq, &g0, &g1);
+    if (g_trace_lat && g0) trace_launch(f, g0, g1);
     // The launch's ranges are complete, except those of a generation that won in it (or in an
     // earlier launch still unseen): handle such wins first, they hand back what did not finish.
-    const uint64_t seq = q_.front().seq;
     for (int s = 0; s < kMaxSlots; ++s) {
       Slot& sl = slots_[s];
       if (sl.state == SlotState::kFree || sl.inflight.empty()) continue;
       if (win_published(s)) handle_win(s);
       size_t m = 0;
-      while (m < sl.inflight.size() && sl.inflight[m].seq <= seq) ++m;
+      while (m < sl.inflight.size() && sl.inflight[m].seq <= f.seq) ++m;
       // dense bounded ranges, hashed in full (fail_all's accounting) -- unless the slot's generation has
       // stopped (won or killed): its launches may have ended part-way, so nothing more is credited
       if (sl.job && sl.job->max_per_dev && !sl.win_seen && sl.stop_us == 0)
@@ -1397,13 +1108,10 @@ int Worker::retire() {
       if (m > 0 && sl.inflight.empty() && sl.state == SlotState::kDraining && !sl.early && sl.job &&
           sl.job->decided.load()) {
         std::lock_guard<std::mutex> g(g_pool.mu);
-        if (sl.job->t_stop[sl.k] == 0) {
-          sl.job->t_stop[sl.k] = now_us();
-          if (g_trace_lat)
-            fprintf(stderr, "nanopow-nofin dev %d ticket %llu slot %d g%llu: stopped at its launch's end, no final "
-                    "count (launch %llu, fin gen %llu)\n", d_.id, (unsigned long long)sl.job->ticket, s,
-                    (unsigned long long)sl.gen, (unsigned long long)seq,
-                    (unsigned long long)__atomic_load_n(&d_.pmb->fin[s].gen, __ATOMIC_ACQUIRE));
+        JobDev& jd = sl.job->dev[sl.k];
+        if (jd.t_stop == 0) {
+          jd.t_stop = now_us();
+          if (g_trace_lat) trace_nofin(s, f.seq);
         }
       }
     }
@@ -1411,21 +1119,25 @@ int Worker::retire() {
       for (Slot& sl : slots_)
         if (sl.state == SlotState::kDraining && sl.job && sl.job->t_win != 0 && sl.job->t_kend == 0)
           sl.job->t_kend = now_us();
-    NPOW_DBGT("nanopow[%d]: launch %llu done\n", d_.id, (unsigned long long)q_.front().seq);
-    retired_seq_ = q_.front().seq;
+    NPOW_DBGT("nanopow[%d]: launch %llu done\n", d_.id, (unsigned long long)f.seq);
+    retired_seq_ = f.seq;
     q_.pop_front();
     publish_counted();
     front_start_ = std::chrono::steady_clock::now();  // the next one (if any) has just started
   }
+  return NPOW_OK;
+}
+
+// The draining slots that no launch holds any more: their counts go to their jobs, which leave the device, are
+// handed back for re-adoption, or (a dropped device) go to the survivors; the slots are freed.
+int Worker::retire_slots() {
   constexpr size_t row = kPoolDoneShards * 8;
   for (int s = 0; s < kMaxSlots; ++s) {
     Slot& sl = slots_[s];
     if (sl.state == SlotState::kDraining && sl.no_readback && sl.inflight.empty()) {
       // finished from its published final count and every launch that held it has completed: nothing can still add
       // to its done counts, so the next job of this slot starts from the published total (sl.baseline)
-      watch_disarm(d_, s);
-      sl.job.reset();
-      sl.state = SlotState::kFree;
+      free_slot(s);
       continue;
     }
     if (sl.state != SlotState::kDraining || !sl.readback) continue;
@@ -1439,16 +1151,7 @@ int Worker::retire() {
       late += d_.h_done[(size_t)s * row + i * 8 + kLateWord];
       stale_hits += d_.h_done[(size_t)s * row + i * 8 + kStaleWord];
     }
-    const uint64_t delta = sum - sl.baseline, late_delta = late - sl.late_base;
-    const uint64_t stale_delta = stale_hits - sl.stale_base;  // (0 for a slot finished from its final count)
-    sl.baseline = sum;
-    sl.late_base = late;
-    sl.stale_base = stale_hits;
-    {
-      std::lock_guard<std::mutex> sg(d_.stats_mu);
-      d_.nonces += delta;
-      d_.late += late_delta;
-    }
+    const Counts c = credit_counts(sl, sum, late, stale_hits);  // (c.stale: 0 for a slot finished from its final count)
     if (win_published(s)) handle_win(s);  // published by the last launch, not yet seen
     if (sl.stale && !sl.fin_seen) {  // every launch that held it has ended: its count came late, or never
       if (__atomic_load_n(&d_.pmb->fin[s].gen, __ATOMIC_ACQUIRE) == sl.gen) {
@@ -1459,37 +1162,32 @@ int Worker::retire() {
         }
         stale_fin_came(s, tw);
       } else {
-        std::lock_guard<std::mutex> sg(d_.stats_mu);
-        d_.stale_missing++;
+        stat([&] { d_.stale_missing++; });
       }
     }
     NPOW_DBG("nanopow[%d]: retire slot %d g%llu done %llu requeue %d early %d\n", d_.id, s,
-             (unsigned long long)sl.gen, (unsigned long long)delta, (int)sl.requeue, (int)sl.early);
+             (unsigned long long)sl.gen, (unsigned long long)c.done, (int)sl.requeue, (int)sl.early);
     if (sl.early) {  // finished by early_finish(): the read-back must add nothing to its count
-      if (delta != 0) {
+      if (c.done != 0) {
         fprintf(stderr, "nanopow: GPU %d slot %d: read back %llu nonces past the published final count\n", d_.id,
-                s, (unsigned long long)delta);
+                s, (unsigned long long)c.done);
         std::lock_guard<std::mutex> sg(d_.stats_mu);
         d_.early_mismatch++;
       }
     } else {
       std::lock_guard<std::mutex> g(g_pool.mu);
       Job& j = *sl.job;
-      j.done += delta;
-      j.late[sl.k] += late_delta;
-      j.stale_hits += stale_delta;
+      credit_job_locked(sl, c);
       if (d_.dead) {
         abandon_locked(sl.job, sl.k, d_.dead_code, d_.dead_msg);  // survivors take what is left
-      } else if (!j.decided && (sl.requeue || !j.todo[sl.k].empty())) {
-        j.on_dev[sl.k] = 0;  // adopt() picks it up again with a fresh generation
+      } else if (!j.decided && (sl.requeue || !j.dev[sl.k].todo.empty())) {
+        j.dev[sl.k].on = false;  // adopt() picks it up again with a fresh generation
         g_pool.version.fetch_add(1);
       } else {
         device_done_locked(sl.job, sl.k);
       }
     }
-    watch_disarm(d_, s);
-    sl.job.reset();
-    sl.state = SlotState::kFree;
+    free_slot(s);
   }
   return NPOW_OK;
 }
@@ -1499,12 +1197,9 @@ int Worker::retire() {
 void Worker::fail_all(const std::string& msg) {
   fprintf(stderr, "nanopow: device %d failed: %s; dropping it\n", d_.id, msg.c_str());
   std::lock_guard<std::mutex> g(g_pool.mu);
-  if (!d_.dead) {
-    d_.dead_code = NPOW_ERR_HIP;
-    d_.dead_msg = "device " + std::to_string(d_.id) + " failed: " + msg;
-    d_.dead = true;
-  }
-  for (Slot& sl : slots_) {
+  if (!d_.dead) drop(NPOW_ERR_HIP, "device " + std::to_string(d_.id) + " failed: " + msg);
+  for (int s = 0; s < kMaxSlots; ++s) {
+    Slot& sl = slots_[s];
     if (sl.state == SlotState::kFree) continue;
     if (sl.job->max_per_dev) {
       // no read-back from a failed device: the job counts its bounded ranges that completed here
@@ -1516,11 +1211,9 @@ void Worker::fail_all(const std::string& msg) {
       const bool stopped = sl.win_seen || sl.stop_us > 0;
       if (!sl.early) sl.job->done += sl.unread + (stopped ? 0 : kept);
     }
-    watch_disarm(d_, (int)(&sl - slots_));  // before the job can end (abandon_locked): the watcher reads its cancel word
-    abandon_locked(sl.job, sl.k, d_.dead_code, d_.dead_msg);
-    sl.job.reset();
-    sl.inflight.clear();
-    sl.state = SlotState::kFree;
+    const JobP j = sl.job;
+    free_slot(s);  // disarmed before the job can end (abandon_locked): the watcher reads its cancel word
+    abandon_locked(j, sl.k, d_.dead_code, d_.dead_msg);
   }
   q_.clear();
   prev_stop_ring_ = -1;
@@ -1547,7 +1240,7 @@ int Worker::step() {
           __atomic_load_n(&d_.pmb->fin[&sl - slots_].gen, __ATOMIC_ACQUIRE) != sl.gen) {
         stale = true;
         if (!sl.stale && lingering) {  // the fallback below fires for it: counted, and classified when the slot's count
-                                       // comes late or not at all (early_finish / retire: stale_missing)
+                                       // comes late or not at all (early_finish / retire_slots: stale_missing)
           sl.stale = true;
           std::lock_guard<std::mutex> sg(d_.stats_mu);
           d_.stale_drains++;
@@ -1562,19 +1255,13 @@ int Worker::step() {
     // the GPU time a lingering launch spends waiting with nothing to hash (its HIP-event time includes it):
     // npow_device_stats.linger_ms, so that kernel_ms - linger_ms is the time the device hashed
     if (lingering && !draining && q_.front().linger) {
-      if (linger_t_ > 0) {
-        std::lock_guard<std::mutex> sg(d_.stats_mu);
-        d_.linger_ms += (t - linger_t_) * 1e-3;
-      }
+      if (linger_t_ > 0) stat([&] { d_.linger_ms += (t - linger_t_) * 1e-3; });
       linger_t_ = t;
     } else {
       linger_t_ = 0;
     }
     bool waiting = d_.tasks_waiting.load() > 0 || d_.dead || g_pool.stopping.load(std::memory_order_relaxed) ||
-                   (stale && !draining) ||
-                   (idle_since_ > 0 && t - idle_since_ > g_linger_us) ||
-                   std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - front_start_).count() >
-                       (double)g_budget_us.load();
+                   (stale && !draining) || (idle_since_ > 0 && t - idle_since_ > g_linger_us) || budget_left_us() < 0;
     for (int s = 0; s < kMaxSlots && !waiting; ++s) waiting = slots_[s].state == SlotState::kActive;  // (fresh)
     if (waiting) {
       end_linger();
@@ -1602,11 +1289,8 @@ int Worker::step() {
 void Worker::run() {
   prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);  // nap(): 1-us timer slack instead of the default 50 us
   t_pool_worker = true;
-  if (hipSetDevice(d_.hip_id) != hipSuccess) {
-    d_.dead_code = NPOW_ERR_HIP;
-    d_.dead_msg = "device " + std::to_string(d_.id) + ": hipSetDevice failed";
-    d_.dead = true;
-  }
+  if (hipSetDevice(d_.hip_id) != hipSuccess)
+    drop(NPOW_ERR_HIP, "device " + std::to_string(d_.id) + ": hipSetDevice failed");
   struct OnExit {
     const Worker& w;
     ~OnExit() {
@@ -1621,7 +1305,7 @@ void Worker::run() {
       std::unique_lock<std::mutex> lk(g_pool.mu);
       for (const JobP& j : std::vector<JobP>(g_pool.active)) {
         const int k = index_in(*j, d_.id);
-        if (k >= 0 && !j->dev_done[k]) abandon_locked(j, (size_t)k, d_.dead_code, d_.dead_msg);
+        if (k >= 0 && !j->dev[k].done) abandon_locked(j, (size_t)k, d_.dead_code, d_.dead_msg);
       }
       if (!g_pool.running) return;
       g_pool.cv_work.wait(lk);
@@ -1764,13 +1448,7 @@ void pool_start() {
     g_pool.running = true;
     g_pool.stopping = false;
   }
-  if (g_watcher_on) {
-    {
-      std::lock_guard<std::mutex> g(g_watch.mu);
-      g_watch.stop = false;
-    }
-    g_watch.th = std::thread(watcher_run);
-  }
+  watch_start();
   for (auto& dp : g_devs) {
     Device* d = dp.get();
     if (d->cpu_threads) {
@@ -1811,16 +1489,7 @@ void pool_stop() {
   }
   for (auto& d : g_devs)
     if (d->worker.joinable()) d->worker.join();
-  if (g_watch.th.joinable()) {
-    {
-      std::lock_guard<std::mutex> g(g_watch.mu);
-      g_watch.stop = true;
-    }
-    g_watch.cv.notify_all();
-    g_watch.th.join();
-  }
-  for (auto& dp : g_devs)  // a worker that left with slots armed (shutdown): nothing is watched any more
-    for (int s = 0; s < kMaxSlots; ++s) watch_disarm(*dp, s);
+  watch_stop();
   std::lock_guard<std::mutex> g(g_pool.mu);
   for (auto& kv : g_pool.tickets) {
     const JobP& j = kv.second;
@@ -1858,20 +1527,12 @@ int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint
   const uint64_t G = devs.size();
   j->spacing = G > 1 ? (~0ull / G) + 1 : 0;  // 2^64 / G (exact for powers of two)
   for (Device* d : devs) j->devs.push_back(d->id);
-  j->todo.resize(G);
+  j->dev.resize(G);
   for (uint64_t k = 0; k < G; ++k) {
     // bounded: max_nonces_per_device; unbounded: the whole stride (2^64 / G; 2^64 - 1 with one device)
     const uint64_t cnt = max_nonces_per_device ? max_nonces_per_device : (G > 1 ? j->spacing : ~0ull);
-    j->todo[k].push_back({start + k * j->spacing, cnt});
+    j->dev[k].todo.push_back({start + k * j->spacing, cnt});
   }
-  j->on_dev.assign(G, 0);
-  j->seen_dev.assign(G, 0);
-  j->dev_done.assign(G, 0);
-  j->dev_slot.assign(G, -1);
-  j->dev_gen.assign(G, 0);
-  j->t_stop.assign(G, 0.0);
-  j->t_launch_dev.assign(G, 0.0);
-  j->late.assign(G, 0);
   j->pending_devs = (int)G;
   j->spin_us = spin_window_us(*j);
   j->t_submit = now_us();
@@ -1897,10 +1558,6 @@ int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint
 // NANOPOW_WAIT_SPIN=0 turns it off (A/B runs).
 constexpr int kMaxSpinners = 2;
 std::atomic<int> g_spinners{0};
-const bool g_wait_spin = [] {
-  const char* e = getenv("NANOPOW_WAIT_SPIN");
-  return !(e && e[0] == '0');
-}();
 
 // Wait, without g_pool.mu, until done() holds (NPOW_OK) or the timeout passes (NPOW_PENDING).  A queued job's
 // cancel word is polled here every 2 ms (admitted ones are polled by the device workers), and such a job is cancelled
@@ -1952,6 +1609,16 @@ static JobP find_ticket(uint64_t ticket) {
   return it == g_pool.tickets.end() ? nullptr : it->second;
 }
 
+// A decided job's outcome as pool_wait and pool_wait_result return it.
+static int outcome(const Job& j, uint64_t* nonce, uint64_t* value) {
+  const int st = j.status;
+  if (st == NPOW_OK) {
+    if (nonce) *nonce = j.nonce;
+    if (value) *value = j.value;
+  }
+  return st < 0 ? fail(st, j.err.empty() ? std::string("work generation failed") : j.err) : st;
+}
+
 int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* value, uint64_t* nonces_done,
               npow_search_info* info) {
   JobP j = find_ticket(ticket);
@@ -1968,8 +1635,8 @@ int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* va
     double worst = 0.0, over = 0.0;
     if (j->t_decide > 0)
       for (size_t k = 0; k < j->devs.size(); ++k) {
-        if ((int)k == j->winner_k || j->t_stop[k] <= j->t_decide) continue;
-        const double span = j->t_stop[k] - j->t_decide;
+        if ((int)k == j->winner_k || j->dev[k].t_stop <= j->t_decide) continue;
+        const double span = j->dev[k].t_stop - j->t_decide;
         worst = std::max(worst, span);
         Device& d = *g_devs[(size_t)j->devs[k]];
         std::lock_guard<std::mutex> sg(d.stats_mu);
@@ -1979,19 +1646,19 @@ int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* va
     info->overshoot_nonces = (uint64_t)over;
     uint64_t dev_late = 0;
     for (size_t k = 0; k < j->devs.size(); ++k)
-      if ((int)k != j->winner_k) dev_late += j->late[k];
+      if ((int)k != j->winner_k) dev_late += j->dev[k].late;
     info->late_nonces_losers = dev_late;
-    info->late_nonces_winner = j->winner_k >= 0 ? j->late[(size_t)j->winner_k] : 0;
+    info->late_nonces_winner = j->winner_k >= 0 ? j->dev[(size_t)j->winner_k].late : 0;
     auto since = [&](double t) { return t > 0 ? t - j->t_submit : 0.0; };
     info->adopt_us = since(j->t_adopt);
     info->launch_us = since(j->t_launch);
     double all = 0.0;
     for (size_t k = 0; k < j->devs.size(); ++k) {
-      if (j->t_launch_dev[k] == 0) {  // a device that never launched it (decided before it got to it; the CPU device)
+      if (j->dev[k].t_launch == 0) {  // a device that never launched it (decided before it got to it; the CPU device)
         all = 0.0;
         break;
       }
-      all = std::max(all, j->t_launch_dev[k]);
+      all = std::max(all, j->dev[k].t_launch);
     }
     info->launch_all_us = since(all);
     info->win_seen_us = since(j->t_win_seen);
@@ -2006,19 +1673,13 @@ int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* va
     if (j->devs.size() > 1 && j->t_decide > 0) {  // the devices' stop times after the decision
       fprintf(stderr, " decide %.1f stops", j->t_decide - j->t_submit);
       for (size_t k = 0; k < j->devs.size(); ++k)
-        fprintf(stderr, " %s%.1f", (int)k == j->winner_k ? "*" : "", j->t_stop[k] > 0 ? j->t_stop[k] - j->t_decide : -1.0);
+        fprintf(stderr, " %s%.1f", (int)k == j->winner_k ? "*" : "",
+                j->dev[k].t_stop > 0 ? j->dev[k].t_stop - j->t_decide : -1.0);
     }
     fprintf(stderr, "\n");
   }
-  const int st = j->status;
   g_pool.tickets.erase(ticket);
-  if (st == NPOW_OK) {
-    if (nonce) *nonce = j->nonce;
-    if (value) *value = j->value;
-    return NPOW_OK;
-  }
-  if (st < 0) return fail(st, j->err.empty() ? std::string("work generation failed") : j->err);
-  return st;
+  return outcome(*j, nonce, value);
 }
 
 // The search's outcome as soon as it is known (npow_wait_result): the winner accepted or the job cancelled,
@@ -2031,15 +1692,7 @@ int pool_wait_result(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint6
           [&] { return j->decided.load(std::memory_order_acquire) || j->finished.load(std::memory_order_acquire); },
           true) == NPOW_PENDING)
     return NPOW_PENDING;
-  // the outcome was written before `decided` was released, and is never written after it
-  const int st = j->status;
-  if (st == NPOW_OK) {
-    if (nonce) *nonce = j->nonce;
-    if (value) *value = j->value;
-    return NPOW_OK;
-  }
-  if (st < 0) return fail(st, j->err.empty() ? std::string("work generation failed") : j->err);
-  return st;
+  return outcome(*j, nonce, value);  // written before `decided` was released, and never after it
 }
 
 int pool_cancel(uint64_t ticket) {
@@ -2060,9 +1713,8 @@ int pool_cancel(uint64_t ticket) {
 
 // Raise a job's weight (npow_promote; the caller checked the weight).  Only the pool lock, as pool_cancel: nothing
 // here waits for a GPU.  A waiting job moves up the admission queue.  An admitted one carries the new weight into
-// every later table and dynamic entry, and for each GPU that holds it now (a slot and a generation) the slot's pinned
-// boost word is written and the device's promotion counter bumped (release: the word first), so that a running
-// counted launch rebalances to the new weight without ending (npow_kernel.hip ls2_promo_relay).  A launch that does
+// every later table and dynamic entry, and each GPU that holds it now (a slot and a generation) is told (mb_boost), so
+// that a running counted launch rebalances to the new weight without ending.  A launch that does
 // not read the counter -- a one-entry one -- or none at all loses nothing: the next table has the weight.
 int pool_promote(uint64_t ticket, uint32_t weight) {
   std::lock_guard<std::mutex> g(g_pool.mu);
@@ -2084,18 +1736,14 @@ int pool_promote(uint64_t ticket, uint32_t weight) {
     }
     return NPOW_OK;
   }
-  for (size_t k = 0; k < j->devs.size(); ++k) {
-    if (!j->on_dev[k] || j->dev_slot[k] < 0) continue;  // (not adopted yet; the CPU device has no slot)
-    Device& d = *g_devs[(size_t)j->devs[k]];
-    if (d.cpu_threads || !d.pmb) continue;
-    __atomic_store_n(&d.pmb->boost[j->dev_slot[k]], pool_boost_word(j->dev_gen[k], pool_wsh(weight)), __ATOMIC_RELEASE);
-    __atomic_fetch_add(&d.pmb->kills, 1ull << 32, __ATOMIC_RELEASE);  // after the word: the high half (promotions)
+  for_each_gpu_slot(*j, [&](size_t, Device& d, JobDev& jd) {
+    mb_boost(d, jd.slot, jd.gen, weight);
     // counted as published into a running launch: a counted launch is in flight and the job is in one
-    if (d.counted_inflight.load(std::memory_order_acquire) > 0 && j->t_launch_dev[k] != 0) {
+    if (d.counted_inflight.load(std::memory_order_acquire) > 0 && jd.t_launch != 0) {
       std::lock_guard<std::mutex> sg(d.stats_mu);
       d.promotions++;
     }
-  }
+  });
   return NPOW_OK;
 }
 
@@ -2104,10 +1752,9 @@ int pool_promote(uint64_t ticket, uint32_t weight) {
 // handle_win compare a win with the threshold under it): once this returns NPOW_OK no result below the threshold
 // can be decided.  The field is all a waiting job needs, or one no slot holds yet: every table and dynamic entry
 // built from now on carries it, and the CPU workers read it at each check.  For each GPU that holds the job in a
-// slot the slot's floor record is written (PoolFloor: the threshold, then the generation with release; the same
-// generation again: one store of the larger threshold), which a wave of a running launch reads when it has a hit
-// (npow_kernel.hip pool_body_ls2) -- no launch ends, and the entry keeps its slot, generation, weight and nonce
-// position.  A win a wave published before it could see the record is refused by handle_win (stale_wins).
+// slot the slot's floor record is written (mb_floor), which a wave of a running launch reads when it has a hit
+// -- no launch ends, and the entry keeps its slot, generation, weight and nonce
+// position.  A win a wave published before it could see the record is refused by Worker::handle_win (stale_wins).
 int pool_retarget(uint64_t ticket, uint64_t threshold) {
   std::lock_guard<std::mutex> g(g_pool.mu);
   auto it = g_pool.tickets.find(ticket);
@@ -2120,18 +1767,7 @@ int pool_retarget(uint64_t ticket, uint64_t threshold) {
   // (Job::spin_us stays as the submit set it: waiters read it without the lock, and a window sized for the old
   // threshold only puts a longer search's waiter and watcher to sleep sooner)
   if (!j->admitted || faults().retarget_blind) return NPOW_OK;
-  for (size_t k = 0; k < j->devs.size(); ++k) {
-    if (!j->on_dev[k] || j->dev_slot[k] < 0) continue;  // (not adopted yet; the CPU device has no slot)
-    Device& d = *g_devs[(size_t)j->devs[k]];
-    if (d.cpu_threads || !d.pmb) continue;
-    PoolFloor& f = d.pmb->floor[j->dev_slot[k]];
-    if (__atomic_load_n(&f.gen, __ATOMIC_RELAXED) != j->dev_gen[k]) {
-      __atomic_store_n(&f.threshold, threshold, __ATOMIC_RELAXED);
-      __atomic_store_n(&f.gen, j->dev_gen[k], __ATOMIC_RELEASE);  // after the threshold
-    } else {
-      __atomic_store_n(&f.threshold, threshold, __ATOMIC_RELEASE);
-    }
-  }
+  for_each_gpu_slot(*j, [&](size_t, Device& d, JobDev& jd) { mb_floor(d, jd.slot, jd.gen, threshold); });
   return NPOW_OK;
 }
 

@@ -1,7 +1,9 @@
-// npow_pool.h -- the work pool's jobs and their state transitions, shared by the GPU workers
-// (npow_pool.cpp) and the CPU workers (npow_cpu.cpp, `--cpu-threads`).  Internal to libnanopow.so.
+// npow_pool.h -- the work pool's jobs and their state transitions (npow_pool.cpp), shared by the GPU workers,
+// the win watcher (npow_pool_watch.cpp) and the CPU workers (npow_cpu.cpp, `--cpu-threads`).
+// Internal to libnanopow.so.
 #pragma once
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <deque>
 #include <memory>
@@ -15,11 +17,28 @@
 namespace npow {
 
 constexpr int kPending = 100;  // job status before it is decided
-double now_us();               // steady clock, microseconds
+inline double now_us() {       // steady clock, microseconds
+  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 
 // [base, base + count) mod 2^64: nonces of a job still to be handed to launches
 struct Range {
   uint64_t base, count;
+};
+
+// A job's state on the k-th of its devices (Job::dev[k]; guarded by g_pool.mu)
+struct JobDev {
+  std::deque<Range> todo;  // ranges not yet handed to a launch (a dead device's remainder is re-strided onto the
+                           // survivors')
+  bool on = false;         // a slot holds the job
+  bool seen = false;       // adopted at least once (re-adoptions do not yield)
+  bool done = false;       // finished with the job
+  int slot = -1;           // the slot holding it while `on` (-1: none; the CPU device has none) ...
+  uint64_t gen = 0;        // ... and its generation there (the decider raises their kill words)
+  double t_stop = 0;       // when its worker saw it stop hashing the job (us; 0 = never adopted)
+  double t_launch = 0;     // when its first launch holding the job was issued (us; 0 = none)
+  uint64_t late = 0;       // nonces its waves hashed after they knew the job was over (device-side count,
+                           // PoolDevState kLateWord)
 };
 
 struct Job {
@@ -33,21 +52,10 @@ struct Job {
   uint32_t weight = 1;    // 1, 2, 4 or 8 (npow_submit_weighted): its share of each GPU's workgroups among the live
                           // unbounded jobs, and its place in the admission queue; the CPU device ignores it
   std::vector<int> devs;  // device ids; the k-th starts on [start + k * spacing, + stride)
-  // guarded by g_pool.mu
-  std::vector<std::deque<Range>> todo;  // per device k: ranges not yet handed to a launch (a dead
-                                        // device's remainder is re-strided onto the survivors')
-  std::vector<uint8_t> on_dev;      // per device k: a slot holds the job
-  std::vector<uint8_t> seen_dev;    // per device k: adopted at least once (re-adoptions do not yield)
-  std::vector<uint8_t> dev_done;    // per device k: finished with the job
-  std::vector<int> dev_slot;        // per device k: the slot holding it while on_dev[k] ...
-  std::vector<uint64_t> dev_gen;    // ... and its generation there (the decider raises their kill words)
-  std::vector<double> t_stop;       // per device k: when its worker saw it stop hashing the job (us; 0 = never adopted)
-  std::vector<double> t_launch_dev; // per device k: when its first launch holding the job was issued (us; 0 = none)
-  std::vector<uint64_t> late;       // per device k: nonces its waves hashed after they knew the job was over
-                                    // (device-side count, PoolDevState kLateWord)
+  std::vector<JobDev> dev;  // per device k of devs; guarded by g_pool.mu
   uint64_t retargets = 0;           // raises of the threshold that took effect (pool_retarget)
   uint64_t stale_hits = 0;          // lanes the devices' waves refused: below the slot's floor (kStaleWord)
-  uint64_t stale_wins = 0;          // wins published under an older threshold, refused and re-armed (handle_win)
+  uint64_t stale_wins = 0;          // wins published under an older threshold, refused and re-armed (Worker::handle_win)
   int winner_k = -1;                // the device whose result decided the job
   int pending_devs = 0;
   std::atomic<bool> admitted{false};  // written under g_pool.mu; waiters read it without it
@@ -74,8 +82,8 @@ struct Job {
   // the deciding one (CPU re-validation then decides at t_decide)
   double t_submit = 0, t_adopt = 0, t_launch = 0, t_win = 0, t_kend = 0, t_finish = 0, t_decide = 0, t_win_seen = 0;
   uint64_t gpu_t_win = 0;  // the deciding win's s_memrealtime (PoolWin::t; NANOPOW_TRACE_LATENCY GPU timelines)
-  double spin_us = 2000.0;  // how long its result waiters and the win watcher poll before they sleep (npow_pool.cpp
-                            // spin_window_us: ~3 x its expected time to a win, in [2, 50] ms)
+  double spin_us = 2000.0;  // how long its result waiters and the win watcher poll before they sleep
+                            // (npow_pool_watch.cpp spin_window_us: ~3 x its expected time to a win, in [2, 50] ms)
 };
 using JobP = std::shared_ptr<Job>;
 
@@ -99,7 +107,15 @@ extern std::atomic<bool> g_exiting;      // process exit, drain over (or its dea
 // Process exit (pool_exit, round 6): the workers drain their launches like pool_stop until this deadline (steady clock
 // us; 0 = not exiting), then leave.  exit_now(): the deadline has passed (it then sets g_exiting) or g_exiting is set.
 extern std::atomic<double> g_exit_deadline_us;
-bool exit_now();
+inline bool exit_now() {
+  if (g_exiting.load(std::memory_order_relaxed)) return true;
+  const double d = g_exit_deadline_us.load(std::memory_order_relaxed);
+  if (d > 0 && now_us() > d) {
+    g_exiting.store(true);
+    return true;
+  }
+  return false;
+}
 
 // The pool lock with its notifications deferred (round 6): the waiters' condition variables and the
 // workers' wakes that decide_locked / finish_locked / stop_other_devices_locked / admit_locked make under it are sent
@@ -126,7 +142,15 @@ void finish_locked(const JobP& j);
 void device_done_locked(const JobP& j, size_t k, double t_seen = 0.0);
 void abandon_locked(const JobP& j, size_t k, int code, const std::string& msg);
 void stop_other_devices_locked(Job& j, size_t k_win);
-int index_in(const Job& j, int dev);  // the job's index of logical device dev, or -1
+// Device k's result (nonce, value), re-validated by the caller and not below the job's threshold, decides job j,
+// which is still pending: the outcome, the timestamps, the winner, and the other devices' kill words.  t_seen: when the
+// win record was read, gpu_t: its PoolWin::t (both 0 for the CPU device, which has no record).
+void accept_win(Job& j, size_t k, uint64_t nonce, uint64_t value, double t_seen, uint64_t gpu_t);
+inline int index_in(const Job& j, int dev) {  // the job's index of logical device dev, or -1
+  for (size_t k = 0; k < j.devs.size(); ++k)
+    if (j.devs[k] == dev) return (int)k;
+  return -1;
+}
 void notify_workers_locked();         // wake the idle workers (cv_work) and the napping ones (each device's wake_cv)
 bool wants_device_locked(int dev);    // some active job wants this device
 

@@ -45,7 +45,7 @@ pytestmark = pytest.mark.gpu
 #   count that is merely late (stale_drains, stale_late: the GPU published it late -- stale_gpu_delay_us, the publish
 #   after the deciding win on the GPU's own clock) is recorded, not asserted: round 6 saw 8 such slots, all of one
 #   search over 8 partitions, i.e. the whole GPU late at once, not a workgroup path that skips the publish.
-NAP_US = 50.0       # npow_pool.cpp g_poll_us: a busy worker's longest nap between looks
+NAP_US = 50.0       # npow_pool_impl.h g_poll_us: a busy worker's longest nap between looks
 PUBLISH_US = 20.0   # the final count's publish (32 loads, one pinned store) and the PCIe hop to the host
 BUDGET_US = 20_000  # the launch's time budget: a loser the kill did not stop hashes until it ends
 SEARCHES = "600"

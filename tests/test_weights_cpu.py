@@ -251,7 +251,7 @@ TABLE_CASES = [
 
 @pytest.fixture(scope="module")
 def table_weights(tmp_path_factory):
-    """pool_table_weights (nano-dpow_amd/csrc/npow_weights.h), the rule Worker::launch builds a table's weights and
+    """pool_table_weights (nano-dpow_amd/csrc/npow_weights.h), the rule Worker::build_table builds a table's weights and
     start map with, compiled into a small program: weights and the grid in, wsum, the halvings and each wsh out."""
     import subprocess
     d = tmp_path_factory.mktemp("tw")
