@@ -72,7 +72,8 @@ extern "C" {
  * Added within revision 7 (the number stays; callers probe for the symbol): npow_promote (raise the weight of a
  * search that is waiting or running), and npow_device_stats gains promotions (still written up to the caller's size);
  * npow_retarget (raise the threshold of a search that is waiting or running; NPOW_TOO_LATE), and npow_search_info
- * gains retargets / stale_hits / stale_wins (likewise written up to the caller's size). */
+ * gains retargets / stale_hits / stale_wins (likewise written up to the caller's size); npow_submit_background (a
+ * search that hashes only on workgroups no other search wants) and npow_ticket_background (its class now). */
 #define NPOW_ABI_VERSION 7
 
 /* Hash paths of npow_values_path. */
@@ -260,6 +261,29 @@ int npow_submit_weighted(const uint8_t root[32], uint64_t threshold, uint64_t st
                          uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint32_t weight,
                          uint64_t* ticket);
 
+/* Queue a background search (added within ABI 7; probe for the symbol): an unbounded search, as npow_submit with
+ * max_nonces_per_device = 0, that each GPU hashes only on the workgroups no foreground search -- every search queued
+ * by the other calls -- wants.  This is a class, not a small weight: while a foreground search is live in a device's
+ * launch, the launch's background searches hold no workgroup there (they keep their slots and nonce positions), and
+ * they get the workgroups back as soon as the foreground searches end -- inside the running launch, nothing ends or
+ * restarts.  Background searches alone share a device equally.  npow_promote(ticket, w) makes the search foreground
+ * with weight w, whether it is waiting, admitted or inside a running launch; npow_retarget and npow_cancel work as on
+ * any search (npow_ticket_background tells how it ended).  Admission: waiting background searches are admitted
+ * after every waiting foreground one, first come first served, only while fewer than max_active searches are live, and
+ * never to more than half of the 64 slots; a foreground search is admitted while fewer than max_active foreground
+ * searches are live and a slot is free, so it never waits behind background ones.  In a launch that holds a bounded
+ * search the device's background searches run as foreground searches of weight 1 for that launch.  The CPU workers
+ * ignore the class. */
+int npow_submit_background(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
+                           const volatile uint32_t* cancel, uint64_t* ticket);
+
+/* The class of an uncollected ticket's search (added within ABI 7; probe for the symbol): *background = 1 while it is
+ * a background search, 0 for a foreground one and once npow_promote has lifted it.  A decided search's class no longer
+ * changes, so read after npow_wait_result and before npow_wait / npow_wait_info it is the class the search ended in.
+ * (npow_search_info keeps its revision-7 layout, which ends with stale_wins.)  NPOW_ERR_BAD_ARGUMENT for an unknown or
+ * collected ticket. */
+int npow_ticket_background(uint64_t ticket, uint32_t* background);
+
 /* Wait up to timeout_us (< 0: forever) for a ticket.  Returns NPOW_PENDING on timeout
  * (the ticket stays valid), otherwise the search's final status exactly as npow_search
  * returns it; the ticket is released then.  Outputs as npow_search. */
@@ -289,7 +313,9 @@ int npow_cancel(uint64_t ticket);
  * promotions counts these) -- and every later launch carries the weight; on each device of a split job, the CPU
  * workers ignoring it.  NPOW_OK and no change for a weight at or below the current one, and for a search already
  * decided or cancelled but not yet collected.  NPOW_ERR_BAD_ARGUMENT for any other weight, an unknown or collected
- * ticket, and a weight above 1 on a bounded search.  Never waits for a GPU.  A weight is never lowered. */
+ * ticket, and a weight above 1 on a bounded search.  Never waits for a GPU.  A weight is never lowered.
+ * A background search (npow_submit_background) becomes a foreground search of weight `weight` -- any of 1, 2, 4, 8 --
+ * in every one of those states; inside a running launch its workgroups arrive through the same rebalancing. */
 int npow_promote(uint64_t ticket, uint32_t weight);
 
 /* Raise the threshold of a search that is waiting, admitted or running (added within ABI 7; probe for the symbol):

@@ -709,6 +709,19 @@ int npow_submit_weighted(const uint8_t root[32], uint64_t threshold, uint64_t st
   return pool_submit(root, threshold, start, device_mask, max_nonces_per_device, cancel, ticket, weight);
 } catch (...) { return guard_exception(); }
 
+int npow_submit_background(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
+                           const volatile uint32_t* cancel, uint64_t* ticket) try {
+  if (int rc = check_init()) return rc;
+  if (!root || !ticket) return fail(NPOW_ERR_BAD_ARGUMENT, "root and ticket are required");
+  return pool_submit(root, threshold, start, device_mask, 0, cancel, ticket, 1, true);
+} catch (...) { return guard_exception(); }
+
+int npow_ticket_background(uint64_t ticket, uint32_t* background) try {
+  if (int rc = check_init()) return rc;
+  if (!background) return fail(NPOW_ERR_BAD_ARGUMENT, "background is required");
+  return pool_ticket_background(ticket, background);
+} catch (...) { return guard_exception(); }
+
 int npow_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce_out, uint64_t* value_out,
               uint64_t* nonces_done) try {
   if (int rc = check_init()) return rc;

@@ -199,12 +199,14 @@ void pool_stop();                    // stop and join the workers (pending jobs 
 bool pool_exit();                    // process exit: drain and join the workers (bounded); false: the drain timed out
 int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
                 uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint64_t* ticket,
-                uint32_t weight = 1);  // weight: 1, 2, 4 or 8 (npow_submit_weighted; checked by the caller)
+                uint32_t weight = 1,  // weight: 1, 2, 4 or 8 (npow_submit_weighted; checked by the caller)
+                bool background = false);  // npow_submit_background (unbounded, weight 1)
 // info (may be null): the search's timeline and overshoot (npow_wait_info)
 int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* value, uint64_t* nonces_done,
               npow_search_info* info = nullptr);
 int pool_wait_result(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* value);
 int pool_cancel(uint64_t ticket);
+int pool_ticket_background(uint64_t ticket, uint32_t* background);  // npow_ticket_background
 int pool_promote(uint64_t ticket, uint32_t weight);  // weight: 1, 2, 4 or 8 (npow_promote; checked by the caller)
 int pool_retarget(uint64_t ticket, uint64_t threshold);  // npow_retarget
 int pool_set_max_active(uint32_t n);

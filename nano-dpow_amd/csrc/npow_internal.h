@@ -116,8 +116,14 @@ struct PoolEntry {
                      // entries' workgroup counts are compared, each is shifted left by its wsh first, so a job's
                      // share of the launch's workgroups is weight / (sum of weights).  Equal values compare as the
                      // plain counts do (kWshOne everywhere: the unweighted pool)
-  uint32_t pad;
+  uint32_t bg;       // unbounded: 1 = a background entry (npow_submit_background; its wsh is kWshOne | kWshBg, the
+                     // flag's copy for the pick): hashed only by
+                     // workgroups that no live foreground entry of the launch wants -- weight 0 in the start map,
+                     // behind every foreground entry in a pick, never a foreground poller's target; counts as
+                     // foreground once the slot's boost mirror carries its generation (pool_eff_background).  0 in
+                     // every entry of a table that holds a bounded entry
 };
+static_assert(sizeof(PoolEntry) == 184, "the background flag took the padding word: the entry keeps its size");
 // (kWshOne, pool_wsh and the table builder's rule pool_table_weights: npow_weights.h)
 static_assert(offsetof(PoolEntry, u) == 0, "the search kernel finds an entry from its uniforms' address");
 struct PoolTable {

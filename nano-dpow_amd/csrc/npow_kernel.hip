@@ -578,18 +578,20 @@ __device__ __forceinline__ ConstEntry* ls2_entry(const PoolTable* tab, const Poo
 // hash does acquire (ls2_choose).
 struct EntryHdr {
   uint64_t gen;
-  uint32_t slot, bounded, wsh;
+  uint32_t slot, bounded, wsh, bg;
 };
 __device__ __forceinline__ EntryHdr ls2_hdr(const PoolTable* tab, PoolMailbox* mb, uint32_t e) {
   if (e < tab->n) {
     ConstEntry* q = (ConstEntry*)(uintptr_t)&tab->e[e];
-    return EntryHdr{q->gen, q->slot, q->bounded, q->wsh};
+    return EntryHdr{q->gen, q->slot, q->bounded, q->wsh, q->bg};
   }
   PoolEntry* q = &mb->dyn[(tab->dyn_base + (e - tab->n)) % kDynRing].e;
+  // (the class from the shift's word, kWshBg: no fifth uncached read per entry and scan)
+  const uint32_t w = __hip_atomic_load(&q->wsh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   return EntryHdr{__hip_atomic_load(&q->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM),
                   __hip_atomic_load(&q->slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM),
-                  __hip_atomic_load(&q->bounded, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM),
-                  __hip_atomic_load(&q->wsh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)};
+                  __hip_atomic_load(&q->bounded, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), w,
+                  (w & kWshBg) ? 1u : 0u};
 }
 // Relaxed: an acquire at system scope invalidates the L2, which at every poll cost 4x the search
 // kernel's fetches.  But a ring position's lines may still sit in an XCD's L2 from an earlier launch
@@ -680,6 +682,14 @@ __device__ __forceinline__ uint32_t ls2_wsh_eff(const PoolTable* tab, PoolDevSta
                       tab->wdown);
 }
 
+// An entry's effective class (pool_eff_background): the flag, and only for a flagged entry of a launch that has
+// relayed a promotion the slot's mirror -- npow_promote lifts a background entry through it.
+__device__ __forceinline__ bool ls2_bg_eff(PoolDevState* st, uint32_t slot, uint64_t gen, uint32_t bg, bool promoted) {
+  if (!bg) return false;
+  if (!promoted) return true;
+  return pool_eff_background(bg, __hip_atomic_load(&st->boost[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), gen);
+}
+
 // A polling wave (lane 0 only): the host words of the entry.  Returns bit 0 set when the wave's
 // workgroup must leave the entry, and bit 1 too when the reason is the pinned kill word: new jobs wait and the entry is unbounded (a yield), it was
 // killed, or it is unbounded and a dynamic entry would, with this workgroup on it, still hold no more workgroups
@@ -757,12 +767,17 @@ __device__ __forceinline__ uint32_t ls2_poll(const PoolTable* tab, PoolDevState*
   // (a launch that has seen a promotion balances toward every live unbounded entry -- a promoted table entry is a
   // target like a dynamic one -- and compares with the effective shifts, the slots' mirrors: the same rule, so the
   // no-ping-pong argument above holds as written)
-  if (!leave && !pe->bounded && (nd > 0 || promoted)) {
+  // (background entries, npow_weights.h: a poller on one looks at every live unbounded entry, as a promoted launch's
+  // do, and leaves for a foreground one whatever the counts; a poller on a foreground entry skips background targets.
+  // Moves across the classes go one way and classes only rise, so the argument still holds.  A launch without a
+  // background entry reads one more word of its own entry here and takes the branches it took.)
+  const bool bgm = tab->counted && ls2_bg_eff(st, pe->slot, pe->gen, pe->bg, promoted);
+  if (!leave && !pe->bounded && (nd > 0 || promoted || bgm)) {
     const unsigned long long mine = ls2_wgs(st, pe->slot);
     const unsigned long long over = __hip_atomic_load(&s_over, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     unsigned long long found = 0;
     const uint32_t sm = promoted ? ls2_wsh_eff(tab, st, pe->slot, pe->gen, pe->wsh) : pe->wsh & 3u;
-    for (uint32_t k = promoted ? 0u : tab->n; k < tab->n + nd && !leave; ++k) {
+    for (uint32_t k = (promoted || bgm) ? 0u : tab->n; k < tab->n + nd && !leave; ++k) {
       if (k == e || ((over >> k) & 1)) continue;
       const EntryHdr q = ls2_hdr(tab, mb, k);
       if (q.bounded || load_dead(st, q.slot) >= q.gen) {
@@ -771,7 +786,7 @@ __device__ __forceinline__ uint32_t ls2_poll(const PoolTable* tab, PoolDevState*
       }
       // (q + 1) << wsh_q <= (mine - 1) << wsh_mine, without the subtraction; equal weights: q + 2 <= mine
       const uint32_t sq = promoted ? ls2_wsh_eff(tab, st, q.slot, q.gen, q.wsh) : q.wsh & 3u;
-      leave = pool_should_move(ls2_wgs(st, q.slot), sq, mine, sm);
+      leave = pool_should_move_class(ls2_bg_eff(st, q.slot, q.gen, q.bg, promoted), ls2_wgs(st, q.slot), sq, bgm, mine, sm);
     }
     ls2_mark_over(found);
   }
@@ -786,16 +801,30 @@ __device__ __forceinline__ uint32_t ls2_choose(const PoolTable* tab, PoolDevStat
   const uint32_t N = tab->n + nd;  // <= kMaxSlots = 64: one lane each
   ls2_fresh(tab, st, nd, seen);
   const bool promoted = ls2_promoted(tab, st);  // (one device-memory word per pick; the mirrors only if so)
+  // The entry the workgroup is leaving is no candidate -- unless it is a background entry: a workgroup that left one
+  // for a foreground entry which has died since picks it again, behind every live foreground entry, instead of
+  // dropping out of the launch while it is live (a yield has killed it by then, and it is skipped as dead).
+  // The class is read from bit 2 of the shift's word (kWshBg, the host's copy of PoolEntry::bg), here and below: a
+  // pick that loaded the flag's own word, or tested it per lane, used more registers, and the hash loop of every
+  // launch, which calls it, reloaded two more spilled SGPRs per iteration (tools/kernel_loop_census.py).
+  const uint32_t ex = e < N && (ls2_entry(tab, mb, e)->wsh & kWshBg) ? kNoEntry : e;
   for (int attempt = 0; attempt < 4; ++attempt) {
     unsigned long long key = ~0ull;
     bool over = false;
     const unsigned long long known = __hip_atomic_load(&s_over, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (lane < N && lane != e && !((known >> lane) & 1)) {
+    if (lane < N && lane != ex && !((known >> lane) & 1)) {
       ConstEntry* q = ls2_entry(tab, mb, lane);
+      const uint32_t qw = q->wsh;
       if (!q->bounded && load_dead(st, q->slot) < q->gen) {
         const uint32_t tie = ((lane + 1u) * 0x9e3779b1u) ^ (g * 0x85ebca6bu);
-        const uint32_t sq = promoted ? ls2_wsh_eff(tab, st, q->slot, q->gen, q->wsh) : q->wsh & 3u;
-        key = ((ls2_wgs(st, q->slot) << sq) << 32) | (tie & ~63u) | lane;
+        uint32_t sq = qw & 3u;
+        bool qbg = (qw & kWshBg) != 0;
+        if (promoted) {
+          const uint64_t mir = __hip_atomic_load(&st->boost[q->slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          sq = pool_eff_wsh(mir, q->gen, qw, tab->wdown);
+          qbg = pool_eff_background(qbg ? 1u : 0u, mir, q->gen);
+        }
+        key = ((unsigned long long)pool_pick_key(qbg, ls2_wgs(st, q->slot), sq) << 32) | (tie & ~63u) | lane;
       } else {
         over = true;
       }
@@ -911,7 +940,9 @@ __device__ __noinline__ uint32_t ls2_pick(const PoolTable* tab, PoolDevState* st
     // the number of entries whose inclusive prefix sum is <= it
     if (tab->wsum) {
       const uint32_t r = pool_start_pos(g, tab->wsum);
-      uint32_t acc = lane < tab->n ? 8u >> (((ConstEntry*)(uintptr_t)&tab->e[lane])->wsh & 3u) : 0u;
+      // (a background entry weighs 0 in a map, pool_table_weights_bg: no workgroup starts on it)
+      ConstEntry* const le = (ConstEntry*)(uintptr_t)&tab->e[lane < tab->n ? lane : 0u];
+      uint32_t acc = lane < tab->n && !le->bg ? 8u >> (le->wsh & 3u) : 0u;
 #pragma unroll
       for (int m = 1; m < 64; m <<= 1) {
         const uint32_t o = __shfl_up(acc, m);

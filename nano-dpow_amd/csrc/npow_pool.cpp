@@ -196,10 +196,22 @@ void decide_locked(Job& j, int status, uint64_t nonce, uint64_t value) {
   notify_waiters(j);  // npow_wait_result returns at the decision
 }
 
+// The waiting queue's front while it may go live.  A foreground job: while fewer than max_active foreground jobs are
+// live and a slot is free -- live background jobs do not count, so it never waits behind them.  A background job
+// (they queue behind every foreground one, queue_rank): only while fewer than max_active jobs are live in all, and
+// background jobs hold fewer than half of the slots.
+constexpr size_t kMaxBackground = kMaxSlots / 2;
 void admit_locked() {
   bool added = false;
-  while (g_pool.active.size() < g_pool.max_active && !g_pool.waiting.empty()) {
+  size_t bg = 0;
+  for (const JobP& a : g_pool.active) bg += a->background ? 1u : 0u;
+  while (!g_pool.waiting.empty() && g_pool.active.size() < (size_t)kMaxSlots) {
+    const bool jbg = g_pool.waiting.front()->background;
+    if (jbg ? (g_pool.active.size() >= g_pool.max_active || bg >= kMaxBackground)
+            : (g_pool.active.size() - bg >= g_pool.max_active))
+      break;
     JobP j = g_pool.waiting.front();
+    bg += jbg ? 1u : 0u;
     g_pool.waiting.pop_front();
     j->admitted = true;
     g_pool.active.push_back(j);
@@ -364,6 +376,7 @@ struct PoolInflight {
   bool counted;         // PoolTable::counted: early finish and dynamic entries are on in it
   bool linger;          // PoolTable::linger: its workgroups wait for dynamic entries until its budget or a yield
   uint32_t wdown;       // its table's weights were halved this many times (pool_table_weights): its dynamic entries' too
+  bool bounded;         // its table holds a bounded entry: no entry of the launch carries the background flag
 };
 
 class Worker {
@@ -431,6 +444,12 @@ class Worker {
   bool live_slot(int except = -1) const {  // a slot (other than `except`) some launch in flight is hashing
     for (int s = 0; s < kMaxSlots; ++s)
       if (s != except && slots_[s].state == SlotState::kActive && !slots_[s].fresh) return true;
+    return false;
+  }
+  bool foreground_live(int except) const {  // live_slot, of a foreground job (caller holds g_pool.mu: Job::background)
+    for (int s = 0; s < kMaxSlots; ++s)
+      if (s != except && slots_[s].state == SlotState::kActive && !slots_[s].fresh && !slots_[s].job->background)
+        return true;
     return false;
   }
   double budget_left_us() const {  // of the running launch's time budget, by the host's estimate of its start
@@ -551,7 +570,9 @@ void Worker::adopt() {
   for (int s = 0; s < kMaxSlots; ++s) {
     Slot& sl = slots_[s];
     if (sl.state != SlotState::kActive || !sl.fresh) continue;
-    if (!dyn_add(s) && sl.new_job) waiting_new = true;
+    // (a new background job that cannot join does not end a launch that hashes a foreground job: it waits for the
+    // next table)
+    if (!dyn_add(s) && sl.new_job && !(sl.job->background && foreground_live(s))) waiting_new = true;
   }
   // the entries published together (one release after all of them): workgroups of a lingering launch that see them
   // spread over all of them at once, where one at a time they would crowd onto the first and rebalance slowly
@@ -570,7 +591,7 @@ void Worker::take_entry(Slot& sl, PoolEntry& pe, uint64_t want, uint64_t seq, do
   pe.threshold = j.threshold;
   pe.gen = sl.gen;
   pe.slot = (uint32_t)(&sl - slots_);
-  pe.pad = 0;
+  pe.bg = 0;
   if (jd.todo.empty()) jd.todo.push_back({j.start, 0});  // cannot happen (adopt / no_more); an empty entry
   Range& r = jd.todo.front();
   pe.base = r.base;
@@ -619,6 +640,10 @@ bool Worker::dyn_add(int s) {
   pe.bounded = 0;
   // the scaled balancing rule (ls2_poll) moves workgroups here up to its weighted share; on the table's scale
   pe.wsh = pool_wsh((j.weight >> f.wdown) ? (j.weight >> f.wdown) : 1u);
+  // a background job (weight 1): parked until the launch's foreground entries end -- but in a launch whose table
+  // holds a bounded entry it runs as a foreground job of weight 1, as the table's own do (build_table)
+  pe.bg = j.background && !f.bounded ? 1u : 0u;
+  if (pe.bg) pe.wsh = kWshOne | kWshBg;
   ctl_ = (ctl_ & ~0xffffffffull) | (uint32_t)(ctl_ + 1);  // the low half wraps on its own (released by adopt())
   stat([&] { d_.dyn++; });
   NPOW_DBGT("nanopow[%d]: dynamic entry %u: slot %d g%llu in launch %llu\n", d_.id, (uint32_t)ctl_ - 1u,
@@ -899,6 +924,7 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
   const uint32_t iters = sh.launch_iters(g_iters.load());
   uint32_t wdown = 0;
   uint32_t weights[kMaxSlots], wshs[kMaxSlots];
+  uint8_t bgs[kMaxSlots];
   t.n = n;
   t.poll_mask = poll_mask();
   t.iters = iters;
@@ -934,6 +960,7 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
       t.e[e].bounded = dense ? 1 : 0;
       t.e[e].wsh = pool_wsh(j.weight);
       weights[e] = j.weight;
+      bgs[e] = j.background ? 1 : 0;
       *bounded = *bounded || dense;
     }
   }
@@ -944,8 +971,14 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
   // entry would stay without one: pool_table_weights (npow_weights.h) halves a crowded table's weights until so.
   t.wsum = 0;
   if (!*bounded) {
-    t.wsum = pool_table_weights(weights, n, (uint32_t)sh.grid, wshs, &wdown);
-    for (uint32_t e = 0; e < n; ++e) t.e[e].wsh = wshs[e];
+    // (background jobs, pool_table_weights_bg: weight 0 in a map beside foreground ones, g % n among themselves.  A
+    // table with a bounded entry carries no background flag -- take_entry cleared it: its background jobs run as
+    // foreground jobs of weight 1 for this launch, since g % n starts workgroups on them)
+    t.wsum = pool_table_weights_bg(weights, bgs, n, (uint32_t)sh.grid, wshs, &wdown);
+    for (uint32_t e = 0; e < n; ++e) {
+      t.e[e].wsh = wshs[e] | (bgs[e] ? kWshBg : 0u);
+      t.e[e].bg = bgs[e];
+    }
   }
   t.wdown = wdown;  // (a promoted weight is published raw: the kernel halves it as the table's were, pool_promoted_wsh)
   t.pad = 0;
@@ -1003,7 +1036,7 @@ int Worker::launch(bool empty_linger) {
             (unsigned long long)seq_, n, t.linger, t.wsum, t.wdown, (unsigned long long)t.yield_base);
   for (uint32_t e = 0; e < n; ++e) NPOW_DBG(" %d/g%llu", idx[e], (unsigned long long)t.e[e].gen);
   NPOW_DBG("\n");
-  q_.push_back({seq_, r, (uint32_t)ctl_, t.yield_base, t.counted != 0, t.linger != 0, t.wdown});
+  q_.push_back({seq_, r, (uint32_t)ctl_, t.yield_base, t.counted != 0, t.linger != 0, t.wdown, bounded});
   publish_counted();
   return NPOW_OK;
 }
@@ -1509,7 +1542,8 @@ void pool_stop() {
 
 // -- jobs -------------------------------------------------------------------------------------------
 int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
-                uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint64_t* ticket, uint32_t weight) {
+                uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint64_t* ticket, uint32_t weight,
+                bool background) {
   // A bounded search over "all devices" (mask 0) leaves the CPU workers out: their stride would be as
   // long as a GPU's at ~1/1000 of its rate, nothing hands their leftover to an idle GPU, and they work on one job
   // at a time -- an exhausting search would wait for them.  An explicit mask may still name the CPU device.
@@ -1524,6 +1558,7 @@ int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint
   j->max_per_dev = max_nonces_per_device;
   j->cancel = cancel;
   j->weight = max_nonces_per_device ? 1u : weight;
+  j->background = background && !max_nonces_per_device;
   const uint64_t G = devs.size();
   j->spacing = G > 1 ? (~0ull / G) + 1 : 0;  // 2^64 / G (exact for powers of two)
   for (Device* d : devs) j->devs.push_back(d->id);
@@ -1541,9 +1576,9 @@ int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint
   j->ticket = g_pool.next_ticket++;
   g_pool.tickets[j->ticket] = j;
   // the waiting queue is kept by weight, heaviest first, FIFO within a weight (admit_locked takes its front):
-  // behind the last job at least as heavy.  With every weight 1 this is the back.
+  // behind the last job at least as heavy.  With every weight 1 this is the back.  Background jobs rank behind all.
   auto at = g_pool.waiting.end();
-  while (at != g_pool.waiting.begin() && (*(at - 1))->weight < j->weight) --at;
+  while (at != g_pool.waiting.begin() && queue_rank(**(at - 1)) < queue_rank(*j)) --at;
   g_pool.waiting.insert(at, j);
   admit_locked();
   *ticket = j->ticket;
@@ -1695,6 +1730,14 @@ int pool_wait_result(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint6
   return outcome(*j, nonce, value);  // written before `decided` was released, and never after it
 }
 
+int pool_ticket_background(uint64_t ticket, uint32_t* background) {
+  std::lock_guard<std::mutex> g(g_pool.mu);
+  auto it = g_pool.tickets.find(ticket);
+  if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  *background = it->second->background ? 1u : 0u;
+  return NPOW_OK;
+}
+
 int pool_cancel(uint64_t ticket) {
   std::lock_guard<std::mutex> g(g_pool.mu);
   auto it = g_pool.tickets.find(ticket);
@@ -1723,17 +1766,22 @@ int pool_promote(uint64_t ticket, uint32_t weight) {
   const JobP& j = it->second;
   if (weight > 1 && j->max_per_dev)
     return fail(NPOW_ERR_BAD_ARGUMENT, "a bounded search (max_nonces_per_device) takes weight 1 only");
-  if (j->finished || j->decided || j->cancel_req || weight <= j->weight) return NPOW_OK;
+  // A background job becomes a foreground job of this weight, whatever the weight: the same steps.  (Admitted, it
+  // may take the live foreground jobs past max_active: it holds its slot already.)
+  const bool lift = j->background;
+  if (j->finished || j->decided || j->cancel_req || (!lift && weight <= j->weight)) return NPOW_OK;
   j->weight = weight;
+  j->background = false;
   if (!j->admitted) {
     // its place in the waiting queue: behind the last job at least as heavy (pool_submit)
     auto at = std::find(g_pool.waiting.begin(), g_pool.waiting.end(), j);
     if (at != g_pool.waiting.end()) {
       JobP keep = *at;
       at = g_pool.waiting.erase(at);
-      while (at != g_pool.waiting.begin() && (*(at - 1))->weight < weight) --at;
+      while (at != g_pool.waiting.begin() && queue_rank(**(at - 1)) < weight) --at;
       g_pool.waiting.insert(at, keep);
     }
+    if (lift) admit_locked();  // (a foreground job does not wait for the live background ones)
     return NPOW_OK;
   }
   for_each_gpu_slot(*j, [&](size_t, Device& d, JobDev& jd) {

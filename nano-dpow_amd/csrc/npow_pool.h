@@ -51,6 +51,9 @@ struct Job {
   const volatile uint32_t* cancel = nullptr;
   uint32_t weight = 1;    // 1, 2, 4 or 8 (npow_submit_weighted): its share of each GPU's workgroups among the live
                           // unbounded jobs, and its place in the admission queue; the CPU device ignores it
+  bool background = false;  // npow_submit_background, until npow_promote lifts it (guarded by g_pool.mu): each GPU
+                            // hashes it only on workgroups no foreground job wants (PoolEntry::bg), and it is admitted
+                            // behind every foreground job; weight stays 1 meanwhile.  The CPU device ignores it
   std::vector<int> devs;  // device ids; the k-th starts on [start + k * spacing, + stride)
   std::vector<JobDev> dev;  // per device k of devs; guarded by g_pool.mu
   uint64_t retargets = 0;           // raises of the threshold that took effect (pool_retarget)
@@ -137,6 +140,8 @@ class PoolLock {
 // -- job state transitions (caller holds g_pool.mu; npow_pool.cpp) ------------------------------
 void decide_locked(Job& j, int status, uint64_t nonce = 0, uint64_t value = 0);
 void admit_locked();
+// A job's rank in the waiting queue (heaviest first, FIFO within a rank): its weight, background jobs behind all
+inline uint32_t queue_rank(const Job& j) { return j.background ? 0u : j.weight; }
 void finish_locked(const JobP& j);
 // t_seen: when the device's worker observed it stop hashing the job (its final count read), 0 = now
 void device_done_locked(const JobP& j, size_t k, double t_seen = 0.0);

@@ -6,6 +6,8 @@
 namespace npow {
 
 constexpr uint32_t kWshOne = 3;  // PoolEntry::wsh of weight 1
+constexpr uint32_t kWshBg = 4;   // bit 2 of PoolEntry::wsh: the entry's background flag again (PoolEntry::bg), for
+                                 // the kernel's pick, which loads this word anyway; every reader of the shift masks & 3
 inline uint32_t pool_wsh(uint32_t weight) {  // weight in {1, 2, 4, 8} -> 3 - log2(weight)
   return weight >= 8 ? 0u : weight >= 4 ? 1u : weight >= 2 ? 2u : 3u;
 }
@@ -86,6 +88,82 @@ inline uint32_t pool_table_weights(const uint32_t* w, uint32_t n, uint32_t grid,
     }
     if (started == (n == 64 ? ~0ull : (1ull << n) - 1)) return sum;
   }
+}
+
+// Background searches (npow_submit_background): an entry is foreground (every search above) or background
+// (PoolEntry::bg).  A background entry is hashed only by workgroups no live foreground entry of its launch wants.
+//  * Effective class: a background entry counts as foreground once its slot's boost mirror carries the entry's own
+//    generation -- npow_promote lifts a background job through the same word and relay that raise a weight.  Classes
+//    only ever change from background to foreground.
+NPOW_HD inline bool pool_eff_background(uint32_t bg_flag, uint64_t mirror, uint64_t gen) {
+  return bg_flag != 0 && (mirror >> 2) != gen;
+}
+//  * Pick order (ls2_choose takes the smallest key): every foreground entry sorts before any background one; within
+//    a class the key is the workgroup count shifted by the entry's wsh, and background entries compare as weight 1
+//    among themselves.  The high 32 bits of the pick key; counts are per XCD shard (< 2^27).
+NPOW_HD inline uint32_t pool_pick_key(bool bg, unsigned long long wgs, uint32_t wsh) {
+  return (bg ? 0x40000000u : 0u) | (uint32_t)(wgs << (bg ? kWshOne : (wsh & 3u)));
+}
+//  * Move rule (ls2_poll): a workgroup on a background entry moves to a live unbounded foreground entry whatever the
+//    counts; one on a foreground entry never moves to a background entry; within a class pool_should_move decides.
+//    Moves across classes go one way only and classes only rise, so no pair of entries admits a move in both
+//    directions: across classes by construction, within one by pool_should_move's own argument.
+NPOW_HD inline bool pool_should_move_class(bool q_bg, unsigned long long q, uint32_t sq, bool mine_bg,
+                                           unsigned long long mine, uint32_t sm) {
+  if (q_bg != mine_bg) return mine_bg;
+  return mine_bg ? pool_should_move(q, kWshOne, mine, kWshOne) : pool_should_move(q, sq, mine, sm);
+}
+//  * Start map: pool_table_weights for a table of n <= 64 unbounded entries of which bg[i] != 0 are background.
+//    No background entry: exactly pool_table_weights.  Only background entries: every wsh is kWshOne and the table is
+//    dealt g % n (returns 0), as an equal-weight table.  Both classes: a background entry weighs 0 in the map (the
+//    kernel gives its lane weight 0, ls2_pick), the returned wsum is the sum of the foreground weights -- non-zero
+//    also when they are all equal, since g % n would start workgroups on the background entries -- and the halving rule
+//    (a workgroup starts on every entry) applies to the foreground entries only: a background entry that starts
+//    with none receives workgroups through ls2_choose once the foreground entries end.  Should the map leave a
+//    foreground entry empty even with every weight at 1 (a grid far smaller than any device's), the flags are
+//    cleared -- bg[] is in/out -- and the table runs as pool_table_weights deals it, its background jobs at weight 1.
+inline uint32_t pool_table_weights_bg(const uint32_t* w, uint8_t* bg, uint32_t n, uint32_t grid, uint32_t* wsh,
+                                      uint32_t* down) {
+  uint32_t nbg = 0;
+  for (uint32_t i = 0; i < n; ++i) nbg += bg[i] ? 1u : 0u;
+  if (nbg == 0 || n > 64) {
+    for (uint32_t i = 0; i < n; ++i) bg[i] = 0;
+    return pool_table_weights(w, n, grid, wsh, down);
+  }
+  *down = 0;
+  if (nbg == n) {
+    for (uint32_t i = 0; i < n; ++i) wsh[i] = kWshOne;
+    return 0;
+  }
+  for (uint32_t k = 0;; ++k) {
+    uint32_t sum = 0, prefix[64];
+    uint64_t want = 0;  // bit i: entry i is foreground
+    bool ones = true;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t eff = bg[i] ? 0u : ((w[i] >> k) ? (w[i] >> k) : 1u);
+      wsh[i] = bg[i] ? kWshOne : pool_wsh(eff);
+      sum += eff;
+      prefix[i] = sum;
+      if (!bg[i]) want |= 1ull << i;
+      ones = ones && eff <= 1u;
+    }
+    *down = k;
+    uint64_t started = 0;
+    for (uint32_t g = 0; g < grid; ++g) {
+      const uint32_t r = pool_start_pos(g, sum);
+      uint32_t e = 0;
+      while (e + 1 < n && prefix[e] <= r) ++e;
+      started |= 1ull << e;
+    }
+    if (started == want) return sum;
+    if (ones) break;
+  }
+  uint32_t plain[64];
+  for (uint32_t i = 0; i < n; ++i) {
+    plain[i] = bg[i] ? 1u : w[i];
+    bg[i] = 0;
+  }
+  return pool_table_weights(plain, n, grid, wsh, down);
 }
 
 }  // namespace npow

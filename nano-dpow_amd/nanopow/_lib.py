@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
+import time
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -47,7 +48,7 @@ EXPORTED_SYMBOLS = (
     "npow_submit", "npow_wait", "npow_cancel", "npow_pool_config", "npow_pool_status",
     "npow_set_pool_tuning", "npow_values_path", "npow_wait_info", "npow_device_stats_get_sized",
     "npow_abi_version", "npow_config_cpu_threads", "npow_wait_result", "npow_submit_weighted",
-    "npow_promote", "npow_retarget",
+    "npow_promote", "npow_retarget", "npow_submit_background", "npow_ticket_background",
 )
 
 
@@ -218,6 +219,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         if hasattr(lib, "npow_retarget"):  # added within ABI 7: probed for
             lib.npow_retarget.argtypes = [u64, u64]
             lib.npow_retarget.restype = ctypes.c_int
+        if hasattr(lib, "npow_submit_background"):  # added within ABI 7: probed for
+            lib.npow_submit_background.argtypes = [u8p, u64, u64, u64, p, pu64]
+            lib.npow_submit_background.restype = ctypes.c_int
+            lib.npow_ticket_background.argtypes = [u64, ctypes.POINTER(ctypes.c_uint32)]
+            lib.npow_ticket_background.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -267,6 +273,7 @@ class Ticket:
         self.ticket = ticket
         self.cancel_token = cancel  # keeps the cancel word alive while the engine may read it
         self.result: Optional[SearchResult] = None
+        self.submitted_background = False  # Engine.submit(background=True): wait_info then reports how it ended
 
     def wait(self, timeout: Optional[float] = None) -> Optional[SearchResult]:
         """Block until the search ends (timeout None) or up to `timeout` seconds; None if
@@ -311,9 +318,23 @@ class Ticket:
         info = SearchInfo()
         info.size = ctypes.sizeof(SearchInfo)
         us = -1 if timeout is None else max(0, int(timeout * 1e6))
+        # info.background (a Python attribute: npow_search_info keeps its layout): 1 if the search ended still
+        # background.  Only a ticket submitted so can: its class is read once the search is decided (it no longer
+        # changes then, npow_ticket_background) and before the ticket is released.
+        ended_bg = 0
+        if self.submitted_background:
+            t0 = time.monotonic()
+            if lib.npow_wait_result(self.ticket, us, None, None) == NPOW_PENDING:
+                return None
+            bg = ctypes.c_uint32(0)
+            _check(lib.npow_ticket_background(self.ticket, ctypes.byref(bg)), lib)
+            ended_bg = bg.value
+            if us >= 0:
+                us = max(0, us - int((time.monotonic() - t0) * 1e6))
         rc = lib.npow_wait_info(self.ticket, us, ctypes.byref(info))
         if rc == NPOW_PENDING:
             return None
+        info.background = ended_bg
         self.cancel_token = None
         _check(rc, lib, ok=(NPOW_OK, NPOW_CANCELLED, NPOW_EXHAUSTED))
         self.result = (SearchResult(rc, info.nonce, info.value, info.nonces_done) if rc == NPOW_OK
@@ -327,6 +348,7 @@ class Ticket:
     def promote(self, weight: int) -> None:
         """Raise the search's weight to max(current, weight), weight in {1, 2, 4, 8} (npow_promote): a waiting
         search moves up the admission queue, a running one gets its new share inside the launch that holds it.
+        A background search (submit(background=True)) becomes a foreground search of that weight, whatever the weight.
         NanoPowError(NPOW_ERR_BAD_ARGUMENT) for another weight, a collected ticket, a bounded search -- and when
         the loaded library has no npow_promote."""
         lib = self.engine.lib
@@ -409,12 +431,26 @@ class Engine:
 
     # -- work pool: asynchronous searches ---------------------------------------------------
     def submit(self, root: bytes, threshold: int, start: int = 0, device_mask: int = 0,
-               max_nonces_per_device: int = 0, cancel: Optional[CancelToken] = None, weight: int = 1) -> "Ticket":
+               max_nonces_per_device: int = 0, cancel: Optional[CancelToken] = None, weight: int = 1,
+               background: bool = False) -> "Ticket":
         """Queue a first-win search and return at once (npow_submit_weighted).  Keep `cancel` alive
         until the ticket's result has been collected (the Ticket holds a reference).
         weight (1, 2, 4 or 8): the search's share of each GPU among the live unbounded searches, weight /
-        (sum of weights), and its place among the jobs waiting for admission (heaviest first)."""
+        (sum of weights), and its place among the jobs waiting for admission (heaviest first).
+        background=True (npow_submit_background; unbounded, weight 1): the search hashes only on workgroups no
+        foreground search wants, until Ticket.promote lifts it.  NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the loaded
+        library has no npow_submit_background, and with max_nonces_per_device or a weight other than 1."""
         t = ctypes.c_uint64(0)
+        if background:
+            if not hasattr(self.lib, "npow_submit_background"):
+                raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_submit_background")
+            if max_nonces_per_device or weight != 1:
+                raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "a background search is unbounded and has weight 1")
+            _check(self.lib.npow_submit_background(_root(root), threshold & M64, start & M64, device_mask,
+                                                   cancel.address if cancel else None, ctypes.byref(t)), self.lib)
+            tk = Ticket(self, t.value, cancel)
+            tk.submitted_background = True
+            return tk
         args = (_root(root), threshold & M64, start & M64, device_mask, max_nonces_per_device,
                 cancel.address if cancel else None)
         if hasattr(self.lib, "npow_submit_weighted"):

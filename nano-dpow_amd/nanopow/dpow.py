@@ -161,7 +161,11 @@ class DpowWorkHandler:
 
     def __init__(self, worker: HttpWorker, publish: PublishFn, payout: str, concurrency: int = 1,
                  rng: Optional[random.Random] = None, weights: Optional[Dict[str, int]] = None,
-                 retarget: bool = False) -> None:
+                 retarget: bool = False, background_types: Tuple[str, ...] = ()) -> None:
+        # background_types (opt-in, e.g. ("precache",)): requests of these work types are sent with
+        # "background": true -- they hash only on what no other search wants -- and rank below every other type, so
+        # the same hash again under any other type (work/ondemand) promotes the search, queued or ongoing
+        self.background_types = frozenset(background_types)
         self.weights = dict(DEFAULT_WEIGHTS if weights is None else weights)
         for t, w in self.weights.items():
             if w not in (1, 2, 4, 8):
@@ -206,6 +210,10 @@ class DpowWorkHandler:
         except MessageError as e:
             log.warning("%s", e)
 
+    def _rank(self, work_type: str) -> int:
+        """A work type's rank: its weight, background types below every weight."""
+        return 0 if work_type in self.background_types else self.weights.get(work_type, 1)
+
     async def queue_work(self, work_type: str, block_hash: str, difficulty: str) -> None:
         if block_hash in self.queue or block_hash in self.ongoing:
             # the same hash again under a heavier type (module docstring): promote it; else ignored as in the reference
@@ -215,7 +223,7 @@ class DpowWorkHandler:
             if self.retarget and _difficulty_above(difficulty, old_difficulty):
                 await self._retarget(block_hash, queued, work_type, difficulty)
                 return
-            if weight <= self.weights.get(old_type, 1) or not _difficulty_not_above(difficulty, old_difficulty):
+            if self._rank(work_type) <= self._rank(old_type) or not _difficulty_not_above(difficulty, old_difficulty):
                 self.stats["ignored"] += 1
                 return
             self.stats["promoted"] += 1
@@ -236,7 +244,7 @@ class DpowWorkHandler:
         """The same hash again at a higher difficulty (module docstring; ``retarget=True``)."""
         old_type = (self.queue[block_hash] if queued else self.ongoing[block_hash])[1]
         weight = self.weights.get(work_type, 1)
-        heavier = weight > self.weights.get(old_type, 1)
+        heavier = self._rank(work_type) > self._rank(old_type)
         self.stats["retargeted"] += 1
         if heavier:
             self.stats["promoted"] += 1
@@ -280,7 +288,9 @@ class DpowWorkHandler:
             try:
                 body = {"action": "work_generate", "hash": block_hash, "difficulty": difficulty}
                 weight = self.weights.get(work_type, 1)
-                if weight != 1:
+                if work_type in self.background_types:
+                    body["background"] = True
+                elif weight != 1:
                     body["weight"] = weight
                 res = await self.worker.post(body)
             except Exception as e:  # noqa: BLE001

@@ -36,6 +36,13 @@ search goes on in place at the higher difficulty (npow_retarget) instead of bein
 cancelled and started again, and a later ``work_generate`` at that difficulty joins
 it.  Difficulties only rise; ``work_generate`` itself still matches a job by hash and
 difficulty and never retargets one.
+A ``work_generate`` with ``"background": true`` (this server's extension; a JSON
+boolean) is a background search: it queues behind every foreground request and its
+search hashes only on the GPU workgroups no foreground search wants
+(npow_submit_background) -- speculative work that costs the other requests nothing.
+A later foreground ``work_generate`` for the same hash and difficulty, or a
+``work_promote`` for the hash, lifts it to a foreground search of that weight, also
+while it runs.  ``status`` reports how many searches in flight are background.
 The reference serves one request at a time; here up to ``max_active`` queued
 requests are handed to libnanopow's work pool at once (npow_submit), where
 every selected GPU searches all of them in the same kernel launches, so a
@@ -76,19 +83,21 @@ class SearchEngine(Protocol):
 
     def submit(self, root: bytes, threshold: int, start: int = 0, device_mask: int = 0,
                max_nonces_per_device: int = 0, cancel: Optional[CancelToken] = None) -> SearchTicket: ...
-    # (an engine that serves weighted requests also takes `weight: int = 1`; passed only when it is not 1)
+    # (an engine that serves weighted requests also takes `weight: int = 1`; passed only when it is not 1 -- and one
+    # that serves background requests `background: bool = False`; passed only when it is set)
 
     def work_value(self, root: bytes, nonce: int) -> int: ...
 
 
 class Job:
     __slots__ = ("root", "threshold", "cancel", "done", "reply", "active", "t_queued", "waiters", "t_started",
-                 "ticket", "dispatched", "collector", "weight")
+                 "ticket", "dispatched", "collector", "weight", "background")
 
-    def __init__(self, root: bytes, threshold: int, weight: int = 1) -> None:
+    def __init__(self, root: bytes, threshold: int, weight: int = 1, background: bool = False) -> None:
         self.root = root
         self.threshold = threshold
-        self.weight = weight
+        self.weight = 1 if background else weight
+        self.background = background  # until a foreground duplicate or a work_promote lifts it
         self.cancel = CancelToken()
         self.done = threading.Event()
         self.reply: Dict[str, Any] = {}
@@ -214,7 +223,8 @@ class WorkServer:
         root = W.parse_hash(req)
         threshold = W.requested_threshold(req, self.base)
         weight = W.parse_weight(req)
-        return self._result(self._enqueue(root, threshold, weight))
+        background = W.parse_background(req)
+        return self._result(self._enqueue(root, threshold, weight, background))
 
     def work_cancel(self, req: Dict[str, Any]) -> Dict[str, Any]:
         root = W.parse_hash(req)
@@ -248,9 +258,11 @@ class WorkServer:
         """Raise the job's weight; True when its search is in the engine and must be promoted there (_promote,
         once the lock is released).  A job still waiting here is submitted with the weight, and so is one whose
         submit is under way: _submit compares the weight again once the ticket exists."""
-        if weight <= job.weight:
+        if job.background:  # lifted: a foreground job of this weight, whatever the weight
+            job.background = False
+        elif weight <= job.weight:
             return False
-        job.weight = weight
+        job.weight = max(job.weight, weight)
         return job.active and job.ticket is not None
 
     def _promote(self, job: Job, weight: int) -> None:
@@ -312,7 +324,11 @@ class WorkServer:
 
     def status(self) -> Dict[str, Any]:
         with self._lock:
-            return {"generating": "1" if self._inflight else "0", "queue_size": str(len(self._queue))}
+            out = {"generating": "1" if self._inflight else "0", "queue_size": str(len(self._queue))}
+            n_bg = sum(1 for j in self._inflight if j.background)
+            if n_bg:  # (this server's extension: how many of the searches in flight are background; absent at 0)
+                out["background"] = str(n_bg)
+            return out
 
     def benchmark(self, req: Dict[str, Any]) -> Dict[str, Any]:
         count = W.parse_count(req)
@@ -331,7 +347,7 @@ class WorkServer:
                 "hint": "Times in milliseconds"}
 
     # -- queue -------------------------------------------------------------------------
-    def _enqueue(self, root: bytes, threshold: int, weight: int = 1) -> Job:
+    def _enqueue(self, root: bytes, threshold: int, weight: int = 1, background: bool = False) -> Job:
         with self._lock:
             if not self._running:
                 j = Job(root, threshold)
@@ -343,11 +359,12 @@ class WorkServer:
                     j.waiters += 1
                     # a heavier duplicate raises a job that still waits here (its place in the queue and the
                     # weight it is submitted with), and promotes one already in the engine (npow_promote)
-                    dup, promote = j, self._raise_locked(j, weight)
+                    # (a foreground duplicate lifts a background job; a background duplicate only shares the result)
+                    dup, promote = j, (not background and self._raise_locked(j, weight))
                     break
             else:
                 dup, promote = None, False
-                job = Job(root, threshold, weight)
+                job = Job(root, threshold, weight, background)
                 self._queue.append(job)
                 ready = self._pump_locked()
         if dup is not None:
@@ -359,11 +376,18 @@ class WorkServer:
 
     def _pump_locked(self) -> List[Job]:
         """Move queued jobs in flight while fewer than max_active are (the heaviest first; within a
-        weight FIFO, or a random one with --shuffle); the caller submits them once the lock is released."""
+        weight FIFO, or a random one with --shuffle); the caller submits them once the lock is released.
+        Background jobs go behind every foreground one, and only while fewer than max_active jobs are in flight in
+        all; a foreground job goes while fewer than max_active foreground ones are, so it never waits behind
+        background jobs (the engine admits by the same rule)."""
         ready = []
-        while self._running and self._queue and len(self._inflight) < self.max_active:
-            top = max(j.weight for j in self._queue)
-            heaviest = [i for i, j in enumerate(self._queue) if j.weight == top]
+        rank = lambda j: 0 if j.background else j.weight  # noqa: E731
+        while self._running and self._queue:
+            top = max(rank(j) for j in self._queue)
+            busy = len(self._inflight) if top == 0 else sum(1 for j in self._inflight if not j.background)
+            if busy >= self.max_active:
+                break
+            heaviest = [i for i, j in enumerate(self._queue) if rank(j) == top]
             idx = self.rng.choice(heaviest) if self.shuffle else heaviest[0]
             job = self._queue.pop(idx)
             job.active = True
@@ -376,14 +400,16 @@ class WorkServer:
         for job in jobs:
             try:
                 # (the keyword only for a weighted request: engines without it keep serving the others)
-                sent, sent_threshold = job.weight, job.threshold
+                sent, sent_threshold, sent_bg = job.weight, job.threshold, job.background
                 extra = {"weight": sent} if sent != 1 else {}
+                if sent_bg:  # (likewise only when asked for)
+                    extra["background"] = True
                 ticket = self.engine.submit(job.root, sent_threshold, start=self.rng.getrandbits(64),
                                             device_mask=self.device_mask, cancel=job.cancel, **extra)
                 with self._lock:  # (a heavier duplicate or a work_retarget may have come while the submit was under way)
                     job.ticket = ticket
-                    now, now_threshold = job.weight, job.threshold
-                if now > sent:
+                    now, now_threshold, now_bg = job.weight, job.threshold, job.background
+                if now > sent or (sent_bg and not now_bg):
                     self._promote(job, now)
                 if now_threshold > sent_threshold:
                     self._retarget(job, now_threshold)

@@ -119,6 +119,17 @@ def requested_threshold(req: Dict[str, Any], base: int) -> int:
 WEIGHTS = (1, 2, 4, 8)
 
 
+def parse_background(req: Dict[str, Any]) -> bool:
+    """The optional ``"background"`` of a work_generate request (a JSON boolean; this server's extension): the
+    search hashes only on what no foreground search wants (npow_submit_background).  False when absent."""
+    b = req.get("background")
+    if b is None:
+        return False
+    if not isinstance(b, bool):
+        raise RequestError("Bad background", "Expecting true or false")
+    return b
+
+
 def parse_weight(req: Dict[str, Any]) -> int:
     """The optional ``"weight"`` of a work_generate or work_promote request (an integer or a decimal string; this server's
     extension -- the reference has no such field): the request's share of each GPU among the searches in

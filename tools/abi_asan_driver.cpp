@@ -74,9 +74,18 @@ static void tickets(int tid, int n) {
     uint64_t ticket = 0;
     const uint64_t thr = (i % 3 == 0) ? 0xffffffffffff0000ull : 0xfffffe0000000000ull;
     // every other ticket weighted (1, 2, 4, 8 in turn): the sorted admission queue and the weighted tables
-    int rc = (i & 1) ? npow_submit_weighted(root, thr, 0, g_mask, 0, &cancel, 1u << ((i >> 1) & 3), &ticket)
-                     : npow_submit(root, thr, 0, g_mask, 0, &cancel, &ticket);
+    // ... and every eighth a background search (npow_submit_background: its place behind the others in that queue,
+    // the admission rule, the flagged entries), some of which the promotion below lifts
+    const bool background = i % 8 == 4;
+    int rc = background ? npow_submit_background(root, thr, 0, g_mask, &cancel, &ticket)
+             : (i & 1) ? npow_submit_weighted(root, thr, 0, g_mask, 0, &cancel, 1u << ((i >> 1) & 3), &ticket)
+                       : npow_submit(root, thr, 0, g_mask, 0, &cancel, &ticket);
     CHECK(rc == NPOW_OK, "submit rc %d", rc);
+    if (background) {
+      uint32_t cls = 9;
+      rc = npow_ticket_background(ticket, &cls);
+      CHECK(rc == NPOW_OK && cls == 1, "ticket_background rc %d class %u", rc, cls);
+    }
     // every third ticket promoted while it waits or runs (npow_promote: the queue's re-ordering, the pinned words)
     if (i % 3 == 1) {
       rc = npow_promote(ticket, 8);
