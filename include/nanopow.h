@@ -42,7 +42,7 @@ extern "C" {
 #define NPOW_CANCELLED 1
 #define NPOW_EXHAUSTED 2
 #define NPOW_PENDING 3             /* npow_wait: timeout elapsed, the ticket is still valid */
-#define NPOW_TOO_LATE 4   /* npow_retarget: the search was already decided or cancelled (not yet collected); unchanged */
+#define NPOW_TOO_LATE 4   /* npow_retarget, npow_relax: the search was already decided or cancelled (not yet collected); unchanged */
 #define NPOW_ERR_NOT_INITIALISED (-1)
 #define NPOW_ERR_NO_DEVICE (-2)
 #define NPOW_ERR_BAD_ARGUMENT (-3)
@@ -73,8 +73,16 @@ extern "C" {
  * search that is waiting or running), and npow_device_stats gains promotions (still written up to the caller's size);
  * npow_retarget (raise the threshold of a search that is waiting or running; NPOW_TOO_LATE), and npow_search_info
  * gains retargets / stale_hits / stale_wins (likewise written up to the caller's size); npow_submit_background (a
- * search that hashes only on workgroups no other search wants) and npow_ticket_background (its class now). */
+ * search that hashes only on workgroups no other search wants) and npow_ticket_background (its class now);
+ * npow_submit_reserve (a search that keeps the best nonce it passes between a reserve threshold and its own),
+ * npow_ticket_reserve (a look at that nonce) and npow_relax (lower the threshold of a running search, answered at once
+ * from the reserve when it qualifies), with NPOW_RESERVE_MIN and npow_reserve_info. */
 #define NPOW_ABI_VERSION 7
+
+/* The lowest reserve threshold npow_submit_reserve takes.  A wave of a search with a reserve enters the kernel's rare
+ * branch whenever one of its 64 lanes meets the reserve: once in 2^14 hashes here (0.06 % even if the branch cost ten
+ * hash times); below it the branch stops being rare.  The receive difficulty, fffffe0000000000, is well inside. */
+#define NPOW_RESERVE_MIN 0xfffff00000000000ull
 
 /* Hash paths of npow_values_path. */
 #define NPOW_PATH_SEARCH 0  /* the instruction stream the search and sweep kernels execute
@@ -319,14 +327,61 @@ int npow_cancel(uint64_t ticket);
 int npow_promote(uint64_t ticket, uint32_t weight);
 
 /* Raise the threshold of a search that is waiting, admitted or running (added within ABI 7; probe for the symbol):
- * the job's threshold becomes max(current, threshold) -- it is never lowered, and a threshold at or below the current
- * one is NPOW_OK with no effect.  Nothing ends or restarts: the search keeps its slot, its weight and its place in the
+ * the job's threshold becomes max(current, threshold) -- this call never lowers it (npow_relax does, for a search
+ * with a reserve), and a threshold at or below the current one is NPOW_OK with no effect.  Nothing ends or restarts: the search keeps its slot, its weight and its place in the
  * nonce space on every device of a split job, the GPUs pass over hits that no longer qualify (npow_search_info
  * stale_hits) and the CPU workers compare with the current threshold.  After NPOW_OK every result the ticket returns
  * has value >= threshold.  NPOW_TOO_LATE when the search was already decided, cancelled or finished (not yet
  * collected): its result stands and may be below `threshold`.  NPOW_ERR_BAD_ARGUMENT for an unknown or collected
  * ticket.  Bounded searches are accepted: the threshold does not touch their coverage.  Never waits for a GPU. */
 int npow_retarget(uint64_t ticket, uint64_t threshold);
+
+/* Queue a search with a reserve threshold (added within ABI 7; probe for the symbol): an unbounded search, as
+ * npow_submit_weighted with max_nonces_per_device = 0 -- a background one with background != 0, as
+ * npow_submit_background (its weight then only checked) -- that also remembers, on each GPU, the best nonce it has
+ * passed whose value is in [reserve, threshold): its reserve.  The hot loop is the same (it compares with `reserve`
+ * and sorts the rare hits afterwards), so the reserve costs nothing per nonce.  npow_ticket_reserve looks at it,
+ * npow_relax lowers the search's threshold to any level down to `reserve`.  reserve == threshold is npow_submit_weighted
+ * / npow_submit_background itself.  NPOW_ERR_BAD_ARGUMENT for reserve > threshold, reserve < NPOW_RESERVE_MIN and a
+ * weight other than 1, 2, 4, 8.  The CPU workers compare with the current threshold and keep no reserve. */
+int npow_submit_reserve(const uint8_t root[32], uint64_t threshold, uint64_t reserve, uint64_t start,
+                        uint64_t device_mask, const volatile uint32_t* cancel, uint32_t weight, uint32_t background,
+                        uint64_t* ticket);
+
+/* A search's reserve (npow_ticket_reserve).  A struct of its own: npow_search_info keeps ending with stale_wins and
+ * npow_device_stats with promotions. */
+typedef struct npow_reserve_info {
+  uint32_t size;        /* set by the caller; the library writes at most that many bytes */
+  uint32_t armed;       /* 1: submitted with reserve < threshold */
+  uint64_t reserve_threshold, threshold;   /* threshold: the current one */
+  uint64_t nonce, value;  /* best reserve held, CPU-validated; value 0 = none yet */
+  int32_t device;       /* logical device that found it; -1 = none */
+  uint32_t answered;    /* 1: npow_relax decided the search from its reserve */
+  uint64_t relaxes;     /* lowerings that took effect */
+  uint64_t candidates;  /* reserve records read from the GPUs and validated */
+} npow_reserve_info;
+
+/* Look at the reserve of an uncollected ticket's search without disturbing it (added within ABI 7; probe for the
+ * symbol): reads the reserve record of every GPU that holds the search, validates each new nonce on the CPU
+ * (npow_work_value) and keeps the best.  A GPU's record is a hint -- only its nonce is used, so a torn or stale
+ * record recomputes to a low value and is dropped; it is never invalid work.  NPOW_OK with out->value == 0 while
+ * there is none.  NPOW_ERR_BAD_ARGUMENT for an unknown or collected ticket, or out / out->size missing.  Never
+ * waits for a GPU. */
+int npow_ticket_reserve(uint64_t ticket, npow_reserve_info* out);
+
+/* Lower the threshold of a search submitted with a reserve (added within ABI 7; probe for the symbol): the
+ * threshold becomes min(current, threshold); *answered (may be null) tells how.  The reserves are harvested as by
+ * npow_ticket_reserve; if the best one has value >= threshold the search is decided from it at once (*answered = 1)
+ * -- its result is available to npow_wait_result before this returns, every device's waves are told to stop and the
+ * final counts arrive as after any win: no GPU wait, no launch.  Otherwise the lowered threshold is published to every
+ * device's running launch and carried by every later one (*answered = 0; a reserve that arrived meanwhile still
+ * answers), and the next lane at or above it wins; nothing ends or restarts.  After NPOW_OK every result the ticket
+ * returns has value >= the lowered threshold.  NPOW_OK with no effect for a threshold at or above the current one.
+ * NPOW_TOO_LATE when the search was already decided or cancelled.  NPOW_ERR_BAD_ARGUMENT for a threshold below the
+ * search's reserve threshold, a search without a reserve, and an unknown or collected ticket.  Composes with
+ * npow_retarget: the current threshold moves both ways and is never below the reserve threshold.  Never waits for a
+ * GPU. */
+int npow_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered);
 
 /* Jobs searched at once (1..64).  Fewer gives the oldest requests every GPU sooner
  * (lower time-to-work under load); more keeps waves busy when jobs end mid-launch. */

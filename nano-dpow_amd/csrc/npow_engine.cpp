@@ -764,6 +764,41 @@ int npow_retarget(uint64_t ticket, uint64_t threshold) try {
   return pool_retarget(ticket, threshold);
 } catch (...) { return guard_exception(); }
 
+int npow_submit_reserve(const uint8_t root[32], uint64_t threshold, uint64_t reserve, uint64_t start,
+                        uint64_t device_mask, const volatile uint32_t* cancel, uint32_t weight, uint32_t background,
+                        uint64_t* ticket) try {
+  if (int rc = check_init()) return rc;
+  if (!root || !ticket) return fail(NPOW_ERR_BAD_ARGUMENT, "root and ticket are required");
+  if (weight != 1 && weight != 2 && weight != 4 && weight != 8)
+    return fail(NPOW_ERR_BAD_ARGUMENT, "weight must be 1, 2, 4 or 8");
+  if (reserve > threshold) return fail(NPOW_ERR_BAD_ARGUMENT, "the reserve threshold must not exceed the threshold");
+  if (reserve < NPOW_RESERVE_MIN)
+    return fail(NPOW_ERR_BAD_ARGUMENT, "the reserve threshold must be at least NPOW_RESERVE_MIN (fffff00000000000)");
+  return pool_submit(root, threshold, start, device_mask, 0, cancel, ticket, background ? 1u : weight, background != 0,
+                     reserve);
+} catch (...) { return guard_exception(); }
+
+int npow_ticket_reserve(uint64_t ticket, npow_reserve_info* out) try {
+  if (int rc = check_init()) return rc;
+  if (!out || out->size < offsetof(npow_reserve_info, reserve_threshold))
+    return fail(NPOW_ERR_BAD_ARGUMENT, "out with out->size set is required");
+  npow_reserve_info full{};
+  const int rc = pool_ticket_reserve(ticket, &full);
+  if (rc != NPOW_OK) return rc;
+  const uint32_t n = std::min<uint32_t>(out->size, (uint32_t)sizeof(full));
+  full.size = n;
+  memcpy(out, &full, n);
+  return NPOW_OK;
+} catch (...) { return guard_exception(); }
+
+int npow_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered) try {
+  if (int rc = check_init()) return rc;
+  uint32_t ans = 0;
+  const int rc = pool_relax(ticket, threshold, &ans);
+  if (answered) *answered = ans;
+  return rc;
+} catch (...) { return guard_exception(); }
+
 int npow_pool_config(uint32_t max_active) try {
   if (int rc = check_init()) return rc;
   return pool_set_max_active(max_active);

@@ -200,7 +200,9 @@ bool pool_exit();                    // process exit: drain and join the workers
 int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
                 uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint64_t* ticket,
                 uint32_t weight = 1,  // weight: 1, 2, 4 or 8 (npow_submit_weighted; checked by the caller)
-                bool background = false);  // npow_submit_background (unbounded, weight 1)
+                bool background = false,  // npow_submit_background (unbounded, weight 1)
+                uint64_t reserve = ~0ull);  // npow_submit_reserve: the reserve threshold (checked by the caller; above
+                                            // the threshold, as the default is: none)
 // info (may be null): the search's timeline and overshoot (npow_wait_info)
 int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* value, uint64_t* nonces_done,
               npow_search_info* info = nullptr);
@@ -209,6 +211,8 @@ int pool_cancel(uint64_t ticket);
 int pool_ticket_background(uint64_t ticket, uint32_t* background);  // npow_ticket_background
 int pool_promote(uint64_t ticket, uint32_t weight);  // weight: 1, 2, 4 or 8 (npow_promote; checked by the caller)
 int pool_retarget(uint64_t ticket, uint64_t threshold);  // npow_retarget
+int pool_ticket_reserve(uint64_t ticket, npow_reserve_info* out);  // npow_ticket_reserve (out: a full struct)
+int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered);  // npow_relax (answered: not null)
 int pool_set_max_active(uint32_t n);
 void pool_counts(uint32_t* queued, uint32_t* active);
 

@@ -122,8 +122,12 @@ struct PoolEntry {
                      // behind every foreground entry in a pick, never a foreground poller's target; counts as
                      // foreground once the slot's boost mirror carries its generation (pool_eff_background).  0 in
                      // every entry of a table that holds a bounded entry
+  uint64_t reserve;  // the entry's reserve threshold (npow_submit_reserve), <= threshold: a wave compares each value
+                     // with this one -- its watch threshold (PoolCursor) -- and only in the hit branch tells wins from
+                     // the lanes in [reserve, current threshold), the reserve candidates (PoolReserve).  Equal to
+                     // threshold in every entry of a search without a reserve: every path is then the one it was
 };
-static_assert(sizeof(PoolEntry) == 184, "the background flag took the padding word: the entry keeps its size");
+static_assert(sizeof(PoolEntry) == 192, "three cache lines: a dynamic entry (PoolDynEntry) holds it exactly");
 // (kWshOne, pool_wsh and the table builder's rule pool_table_weights: npow_weights.h)
 static_assert(offsetof(PoolEntry, u) == 0, "the search kernel finds an entry from its uniforms' address");
 struct PoolTable {
@@ -231,7 +235,20 @@ struct PoolDevState {
   // boost[slot]: pool_boost_mirror of the slot's latest relayed word, raised with an atomic max (npow_weights.h).
   alignas(64) unsigned long long promo_done[kPoolRing][8];
   alignas(64) unsigned long long boost[kMaxSlots];
+  // Reserve hits (npow_submit_reserve): the best reserve candidate of each slot's current generation, as
+  // pool_reserve_key(gen, value), raised with a device-scope atomic max in the hit branch (pool_body_ls2); the lane
+  // that raised it stores its nonce to the slot's PoolReserve record.  The generation leads the key and a slot's
+  // generations only grow, so the first candidate of a new generation beats whatever the last one left: arming the
+  // slot (its entry's generation, written by the host) resets the word without a write to device memory.
+  alignas(64) unsigned long long reserve_best[kMaxSlots];
 };
+// The key of a reserve candidate: the slot's generation above 24 bits of the value.  Reserve thresholds are at least
+// NPOW_RESERVE_MIN (fffff00000000000), so a candidate's top 20 bits are ones and bits 43..20 order candidates to one
+// part in 2^24 of that range; two that tie there are as good as each other.  Generations stay below 2^40 (one per
+// adoption: centuries at any rate a GPU can be armed).
+__host__ __device__ inline unsigned long long pool_reserve_key(uint64_t gen, uint64_t value) {
+  return (unsigned long long)((gen << 24) | ((value >> 20) & 0xffffffull));
+}
 
 // Pinned host-coherent mailbox of the pool: one win record per slot (the winner stores
 // nonce and value, then releases gen) and one kill word per slot the host raises.
@@ -266,17 +283,28 @@ struct alignas(64) PoolFin {
   uint64_t stale;  // the slot's stale-hit words, summed (kStaleWord; cumulative, stored before gen like total and late)
 };
 static_assert(sizeof(PoolFin) == 64, "one line per slot");
-// The floor of a slot's threshold (npow_retarget): the host raised the threshold of the job that generation `gen`
-// of the slot searches.  It writes the threshold first and then releases the generation; a second raise for the
+// The floor of a slot's threshold (npow_retarget, npow_relax): the host moved the threshold of the job that generation
+// `gen` of the slot searches -- raised it, or (a search with a reserve) lowered it; the record carries the current one.
+// It writes the threshold first and then releases the generation; a second raise for the
 // same generation is one 64-bit store of a larger threshold.  A wave reads the record only when it has a hit
 // (pool_body_ls2): the generation first and, if it is its entry's, then the threshold, both past the caches, and
-// takes the threshold as its own when it is above the one it holds.  A slot gets its next
+// takes it as the job's current threshold (a wave without a reserve keeps it as its own when it is above the one it
+// holds).  A slot gets its next
 // generation only after every workgroup has left the previous one (its final count, or its launches' end), so no
 // wave of an older generation reads a record while the host rewrites it for a newer one; a record of another
 // generation is ignored.
 struct alignas(16) PoolFloor {
   uint64_t threshold;
   uint64_t gen;
+};
+// The reserve of a slot (npow_submit_reserve): the nonce of the best value in [reserve, current threshold) that a wave
+// of generation `gen` has seen so far, stored by the lane whose candidate raised PoolDevState::reserve_best -- the
+// nonce, then the generation, released, as a win record is.  A hint only: the host recomputes the nonce's value
+// (pool_harvest_locked) and trusts nothing else, so a record torn between two publishers, or one that holds the
+// lesser of two candidates published microseconds apart, costs a candidate and never yields invalid work.
+struct alignas(16) PoolReserve {
+  uint64_t gen;
+  uint64_t nonce;
 };
 // An unbounded job adopted while a search launch runs joins that launch instead of ending it
 // (a yield): the host writes its entry at ring position p (dyn[p % kDynRing]) and then releases
@@ -290,7 +318,6 @@ constexpr int kDynEntries = 32;
 constexpr int kDynRing = 2 * kDynEntries;
 struct alignas(64) PoolDynEntry {
   PoolEntry e;
-  uint8_t pad[192 - sizeof(PoolEntry)];
 };
 static_assert(sizeof(PoolDynEntry) == 192, "3 cache lines per dynamic entry");
 struct PoolMailbox {
@@ -300,7 +327,9 @@ struct PoolMailbox {
   uint64_t kill[kMaxSlots];  // kill[s] = gen: the job in slot s (that generation) must stop
   uint64_t boost[kMaxSlots];  // boost[s] = pool_boost_word(gen, wsh): the job in slot s (that generation) was promoted
                               // to the weight of that shift (npow_promote; written before the counter below is bumped)
-  PoolFloor floor[kMaxSlots];  // floor[s]: the raised threshold of the job in slot s (npow_retarget; PoolFloor)
+  PoolFloor floor[kMaxSlots];  // floor[s]: the current threshold of the job in slot s once it moved (npow_retarget,
+                               // npow_relax; PoolFloor)
+  PoolReserve reserve[kMaxSlots];  // reserve[s]: the best reserve candidate of the job in slot s (PoolReserve)
   // High half: bumped by the host when new jobs wait for the next launch (a yield); low half: the
   // dynamic entries published (ring positions, see PoolDynEntry).  One word, so a poll reads both
   // with one uncached read.

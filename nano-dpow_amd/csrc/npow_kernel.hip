@@ -276,7 +276,8 @@ __global__ __launch_bounds__(kLsBlock, 8) void npow_values_kernel_ls2(const Laun
 // search.
 struct PoolCursor {
   const uint64_t* up;  // the entry's uniforms in memory (the stream loads them itself)
-  uint64_t threshold, base, gen;
+  uint64_t threshold, base, gen;  // threshold: the wave's watch threshold -- the entry's reserve (PoolEntry::reserve;
+                                  // the entry's threshold itself in a search without one)
   uint32_t slot;
   uint32_t K, j;      // block index b = it * K + j; nonce = base + b * 64 + lane
   uint32_t it_end;    // the wave runs the entry while it < it_end
@@ -296,7 +297,7 @@ __device__ __forceinline__ uint64_t load_dead(PoolDevState* st, uint32_t slot) {
 __device__ __forceinline__ void pool_load_ls(const PoolEntry* __restrict__ pe, PoolCursor& c, uint32_t g, uint32_t wv,
                                              uint32_t G, uint32_t n, uint32_t e, uint32_t iters) {
   c.up = pe->u;
-  c.threshold = pe->threshold;
+  c.threshold = pe->reserve;
   c.base = pe->base;
   c.gen = pe->gen;
   c.slot = pe->slot;
@@ -557,6 +558,17 @@ __device__ __forceinline__ void ls2_publish_win(PoolDevState* st, PoolMailbox* m
     __hip_atomic_store(&pw->t, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(&pw->gen, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     // the winner's own workgroup is on the entry: its leave publishes, after the win record
+  }
+}
+
+// A reserve candidate (pool_body_ls2's hit branch): raise the slot's best key; whoever raised it stores the nonce.
+__device__ __forceinline__ void ls2_publish_reserve(PoolDevState* st, PoolMailbox* mb, uint32_t slot, uint64_t gen,
+                                                    uint64_t rn, uint64_t rv) {
+  const unsigned long long key = pool_reserve_key(gen, rv);
+  if (__hip_atomic_fetch_max(&st->reserve_best[slot], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < key) {
+    PoolReserve* pr = &mb->reserve[slot];
+    __hip_atomic_store(&pr->nonce, rn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&pr->gen, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -1097,19 +1109,45 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
         PoolFloor* const fl = &mb->floor[wslot];
         const uint64_t fgen = __hip_atomic_load(&fl->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         ls2_complete();
-        uint64_t floor = 0;
+        // Reserve hits (npow_submit_reserve): thr is the wave's watch threshold, the entry's reserve, and the hit
+        // lanes are sorted here.  The job's current threshold is the floor record's under this generation's tag (it
+        // carries every raise and every lowering, npow_relax) and the entry's own otherwise, re-read from the entry
+        // like its slot.  Lanes at or above it win as ever; lanes that met the entry's threshold but not the current
+        // one are the stale hits above; the rest, in [watch, current), are reserve candidates.  An entry without a
+        // reserve has watch == threshold: no lane is a candidate, and a floor above the watch becomes the watch.
+        const uint64_t ethr = ce->threshold;
+        uint64_t cur = ethr;
         if (uni64(fgen) == wgen) {
           const uint64_t fthr = __hip_atomic_load(&fl->threshold, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           ls2_complete();
-          floor = uni64(fthr);
+          cur = uni64(fthr);
         }
-        if (floor > thr) {
-          c.threshold = floor;
-          const uint64_t keep = hits & __ballot(value >= floor);  // (hits: under the BOUNDED lane mask)
-          if (lane == 0)
+        const bool armed = ce->reserve != ethr;
+        if (cur > thr) {
+          if (!armed) c.threshold = cur;
+          const uint64_t keep = hits & __ballot(value >= cur);  // (hits: under the BOUNDED lane mask)
+          const uint64_t stale = hits & ~keep & __ballot(value >= ethr);
+          if (stale != 0 && lane == 0)
             atomicAdd(&st->done[wslot][(blockIdx.x % kPoolDoneShards) * 8 + kStaleWord],
-                      (unsigned long long)__builtin_popcountll(hits & ~keep));
+                      (unsigned long long)__builtin_popcountll(stale));
+          uint64_t cand = hits & ~keep & ~stale;
           hits = keep;
+          if (cand != 0) {
+            // the wave's best candidate (nearly always its only one), then one lane: a device-scope max on the
+            // slot's best key and, only if that rose, the nonce to the slot's pinned record -- the nonce, then the
+            // generation, as a win record is written.  No stop request, no dead word: the workgroup goes on.
+            uint64_t bv = 0, bn = 0;
+            do {
+              const int cl = __builtin_ctzll(cand);
+              cand &= cand - 1;
+              const uint64_t cv = readlane64(value, cl);
+              if (cv >= bv) {
+                bv = cv;
+                bn = readlane64(nonce, cl);
+              }
+            } while (cand != 0);
+            if (lane == 0) ls2_publish_reserve(st, mb, wslot, wgen, bn, bv);
+          }
         }
         if (hits != 0) {
           why = 2u;

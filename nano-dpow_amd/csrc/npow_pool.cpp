@@ -589,6 +589,7 @@ void Worker::take_entry(Slot& sl, PoolEntry& pe, uint64_t want, uint64_t seq, do
   JobDev& jd = j.dev[sl.k];
   memcpy(pe.u, j.u, sizeof(pe.u));
   pe.threshold = j.threshold;
+  pe.reserve = j.armed ? j.reserve : pe.threshold;  // (no reserve: the waves' watch threshold is the entry's own)
   pe.gen = sl.gen;
   pe.slot = (uint32_t)(&sl - slots_);
   pe.bg = 0;
@@ -1543,7 +1544,7 @@ void pool_stop() {
 // -- jobs -------------------------------------------------------------------------------------------
 int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
                 uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint64_t* ticket, uint32_t weight,
-                bool background) {
+                bool background, uint64_t reserve) {
   // A bounded search over "all devices" (mask 0) leaves the CPU workers out: their stride would be as
   // long as a GPU's at ~1/1000 of its rate, nothing hands their leftover to an idle GPU, and they work on one job
   // at a time -- an exhausting search would wait for them.  An explicit mask may still name the CPU device.
@@ -1554,6 +1555,8 @@ int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint
   j->pre = host_precompute(root);
   npow_asm_uniforms(j->pre.m, j->u);
   j->threshold = threshold;
+  j->armed = reserve < threshold && !max_nonces_per_device;
+  j->reserve = j->armed ? reserve : threshold;
   j->start = start;
   j->max_per_dev = max_nonces_per_device;
   j->cancel = cancel;
@@ -1816,6 +1819,98 @@ int pool_retarget(uint64_t ticket, uint64_t threshold) {
   // threshold only puts a longer search's waiter and watcher to sleep sooner)
   if (!j->admitted || faults().retarget_blind) return NPOW_OK;
   for_each_gpu_slot(*j, [&](size_t, Device& d, JobDev& jd) { mb_floor(d, jd.slot, jd.gen, threshold); });
+  return NPOW_OK;
+}
+
+// Read the reserve records of every GPU slot that holds job j (caller holds g_pool.mu; no GPU call: pinned host
+// memory).  A record is a hint (PoolReserve): only its nonce is used, and its value is recomputed here, so a torn
+// record, or one a slot's earlier generation left, comes out below the reserve threshold and is dropped.  Each
+// record is validated once (JobDev::res_seen); the job keeps the best.
+static void pool_harvest_locked(Job& j) {
+  for_each_gpu_slot(j, [&](size_t k, Device& d, JobDev& jd) {
+    const PoolReserve& r = d.pmb->reserve[jd.slot];
+    if (__atomic_load_n(&r.gen, __ATOMIC_ACQUIRE) != jd.gen) return;
+    const uint64_t n = __atomic_load_n(&r.nonce, __ATOMIC_RELAXED);
+    if (jd.res_seen_gen == jd.gen && jd.res_seen == n) return;
+    jd.res_seen_gen = jd.gen;
+    jd.res_seen = n;
+    j.candidates++;
+    const uint64_t v = host_work_value(j.pre.m, n);
+    if (v >= j.reserve && v > j.res_value) {
+      j.res_nonce = n;
+      j.res_value = v;
+      j.res_dev = j.devs[k];
+    }
+  });
+}
+
+// Decide job j from its reserve (caller holds g_pool.mu; the reserve meets the current threshold): the way a win
+// of another device goes -- the outcome is set and its waiters are told before this returns, the kill word of every
+// device that holds the job goes up, the finder's included (its waves know of no win), and each worker then retires
+// its slot from the final count its launch publishes (check_slots, early_finish).
+static void pool_answer_locked(Job& j) {
+  const int k = index_in(j, j.res_dev);
+  accept_win(j, k >= 0 ? (size_t)k : 0u, j.res_nonce, j.res_value, 0.0, 0);
+  j.answered = true;
+  if (k >= 0) {
+    JobDev& jd = j.dev[(size_t)k];
+    Device& d = *g_devs[(size_t)j.devs[(size_t)k]];
+    if (jd.on && jd.slot >= 0 && !d.cpu_threads && d.pmb) mb_kill(d, jd.slot, jd.gen);
+  }
+  g_pool.decisions.fetch_add(1, std::memory_order_release);
+  notify_workers_locked();
+}
+
+int pool_ticket_reserve(uint64_t ticket, npow_reserve_info* out) {
+  std::lock_guard<std::mutex> g(g_pool.mu);
+  auto it = g_pool.tickets.find(ticket);
+  if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  Job& j = *it->second;
+  if (j.armed && !j.decided && !j.finished) pool_harvest_locked(j);
+  out->armed = j.armed ? 1u : 0u;
+  out->reserve_threshold = j.reserve;
+  out->threshold = j.threshold.load(std::memory_order_relaxed);
+  out->nonce = j.res_nonce;
+  out->value = j.res_value;
+  out->device = j.res_value ? j.res_dev : -1;
+  out->answered = j.answered ? 1u : 0u;
+  out->relaxes = j.relaxes;
+  out->candidates = j.candidates;
+  return NPOW_OK;
+}
+
+// Lower a job's threshold (npow_relax).  Only the pool lock, as pool_retarget: nothing here waits for a GPU, and the
+// lock orders the lowering against every decision.  The reserves are harvested first: one that meets the new
+// threshold decides the job at once.  Otherwise the field is lowered -- every table and dynamic entry built from now
+// on carries it, the CPU workers read it at each check -- and each GPU slot's floor record is rewritten (mb_floor),
+// which a wave of a running launch reads when a lane meets its watch threshold: lanes at or above the new threshold
+// win from then on.  Then a second harvest: a candidate that was on its way to the pinned record while the first
+// one ran (its wave had read the old threshold) has landed or will be seen as a win by a later wave; the one that
+// has landed may qualify now.
+int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered) {
+  JobP j;      // (declared before the lock: the job decided under it stays referenced past the lock's scope)
+  PoolLock g;
+  auto it = g_pool.tickets.find(ticket);
+  if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  j = it->second;
+  if (!j->armed) return fail(NPOW_ERR_BAD_ARGUMENT, "the search was submitted without a reserve threshold");
+  if (threshold < j->reserve) return fail(NPOW_ERR_BAD_ARGUMENT, "below the search's reserve threshold");
+  if (j->finished || j->decided || j->cancel_seen()) return NPOW_TOO_LATE;  // its outcome stands
+  if (threshold >= j->threshold.load(std::memory_order_relaxed)) return NPOW_OK;
+  j->relaxes++;
+  pool_harvest_locked(*j);
+  if (j->res_value < threshold) {
+    j->threshold.store(threshold, std::memory_order_release);
+    if (j->admitted)
+      for_each_gpu_slot(*j, [&](size_t, Device& d, JobDev& jd) { mb_floor(d, jd.slot, jd.gen, threshold); });
+    pool_harvest_locked(*j);
+  } else {
+    j->threshold.store(threshold, std::memory_order_release);
+  }
+  if (j->res_value >= threshold) {
+    pool_answer_locked(*j);
+    *answered = 1;
+  }
   return NPOW_OK;
 }
 

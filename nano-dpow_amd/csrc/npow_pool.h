@@ -35,6 +35,8 @@ struct JobDev {
   bool done = false;       // finished with the job
   int slot = -1;           // the slot holding it while `on` (-1: none; the CPU device has none) ...
   uint64_t gen = 0;        // ... and its generation there (the decider raises their kill words)
+  uint64_t res_seen = 0;   // the nonce of the slot's reserve record at the last harvest of this generation, and ...
+  uint64_t res_seen_gen = 0;  // ... that generation (pool_harvest_locked validates a record once)
   double t_stop = 0;       // when its worker saw it stop hashing the job (us; 0 = never adopted)
   double t_launch = 0;     // when its first launch holding the job was issued (us; 0 = none)
   uint64_t late = 0;       // nonces its waves hashed after they knew the job was over (device-side count,
@@ -45,8 +47,18 @@ struct Job {
   uint64_t ticket = 0;
   RootPrecomp pre{};
   uint64_t u[NPOW_ASM_N_UNIFORMS] = {};
-  std::atomic<uint64_t> threshold{0};  // written under g_pool.mu (pool_submit, pool_retarget: it only rises); the
-                                       // win watcher, the GPU workers and the CPU workers read it without the lock
+  std::atomic<uint64_t> threshold{0};  // written under g_pool.mu (pool_submit; pool_retarget raises it, pool_relax
+                                       // lowers it, never below `reserve`); the win watcher, the GPU workers and the
+                                       // CPU workers read it without the lock
+  // Reserve hits (npow_submit_reserve; all guarded by g_pool.mu).  reserve: the reserve threshold, <= threshold at the
+  // submit; equal to it for every other submit (not armed): such a job's entries, waves and records are as before.
+  uint64_t reserve = 0;
+  bool armed = false;               // reserve < threshold at the submit
+  uint64_t res_nonce = 0, res_value = 0;  // the best reserve validated so far (pool_harvest_locked); value 0 = none
+  int res_dev = -1;                 // the logical device whose record held it
+  bool answered = false;            // pool_relax decided the job from its reserve
+  uint64_t relaxes = 0;             // lowerings of the threshold that took effect (pool_relax)
+  uint64_t candidates = 0;          // reserve records read from the GPUs and validated
   uint64_t start = 0, max_per_dev = 0, spacing = 0;
   const volatile uint32_t* cancel = nullptr;
   uint32_t weight = 1;    // 1, 2, 4 or 8 (npow_submit_weighted): its share of each GPU's workgroups among the live

@@ -82,10 +82,10 @@ inline void mb_boost(Device& d, int s, uint64_t gen, uint32_t weight) {
   __atomic_store_n(&d.pmb->boost[s], pool_boost_word(gen, pool_wsh(weight)), __ATOMIC_RELEASE);
   __atomic_fetch_add(&d.pmb->kills, 1ull << 32, __ATOMIC_RELEASE);
 }
-// Raise the threshold of slot s, generation gen: its floor record (PoolFloor), which a wave reads when it has a hit
-// (npow_kernel.hip pool_body_ls2), so no counter.  The threshold goes before the generation, which is released: a
-// wave that reads this generation then reads this threshold or a later, larger one.  The same generation again (a
-// second raise): one store of the larger threshold.
+// Move the threshold of slot s, generation gen -- a raise (pool_retarget) or a lowering (pool_relax): its floor record
+// (PoolFloor), which a wave reads when it has a hit (npow_kernel.hip pool_body_ls2), so no counter.  The threshold goes
+// before the generation, which is released: a wave that reads this generation then reads this threshold or a later
+// one.  The same generation again (a second move): one store of the new threshold.
 inline void mb_floor(Device& d, int s, uint64_t gen, uint64_t threshold) {
   PoolFloor& f = d.pmb->floor[s];
   if (__atomic_load_n(&f.gen, __ATOMIC_RELAXED) != gen) {

@@ -50,6 +50,12 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="No effect on the work server itself (it takes each request's weight from the request's "
                          "\"weight\" field). The weight (1, 2, 4 or 8) that a DPoW work handler built from these options "
                          "(dpow_weights) puts on its on-demand requests; precache ones keep weight 1.")
+    ap.add_argument("--reserve-difficulty", "--reserve_difficulty", dest="reserve_difficulty", default=None,
+                    metavar="HEX",
+                    help="Off by default. Every work_generate above this difficulty (at least fffff00000000000; the "
+                         "receive difficulty is fffffe0000000000) is searched with it as its reserve: a later request "
+                         "for the same hash at a lower difficulty, or a work_relax, is answered from the best nonce the "
+                         "running search has passed.")
     ap.add_argument("--base-difficulty", default=W.fmt_u64(W.DEFAULT_BASE),
                     help="Threshold multipliers are quoted against (default fffffff800000000).")
     ap.add_argument("-v", "--verbose", action="store_true")
@@ -92,6 +98,9 @@ def build(args: argparse.Namespace):
         return 2
     try:
         base = W.parse_threshold(args.base_difficulty)
+        reserve = None if args.reserve_difficulty is None else W.parse_threshold(args.reserve_difficulty)
+        if reserve is not None and reserve < W.RESERVE_MIN:
+            raise ValueError(f"--reserve-difficulty must be at least {W.RESERVE_MIN:016x}")
         gpus = [W.parse_gpu_spec(s) for s in args.gpu]
         host, _, port = args.listen.rpartition(":")
         host = host.strip("[]") or "127.0.0.1"
@@ -119,7 +128,7 @@ def build(args: argparse.Namespace):
         return 2
     apply_threads(eng, gpus)
     srv = HttpWorkServer(WorkServer(eng, base_threshold=base, shuffle=args.shuffle, device_mask=mask,
-                                    max_active=args.max_active), host, port_i)
+                                    max_active=args.max_active, reserve_threshold=reserve), host, port_i)
     logging.info("Configured for the live network with threshold %016x", base)
     logging.info("Ready to receive requests on %s (%d GPU(s)%s, %s)", srv.address,
                  bin(mask & eng.gpu_mask).count("1") if mask else n_gpus,

@@ -23,7 +23,7 @@ NPOW_OK = 0
 NPOW_CANCELLED = 1
 NPOW_EXHAUSTED = 2
 NPOW_PENDING = 3
-NPOW_TOO_LATE = 4  # npow_retarget: the search was already decided or cancelled (not yet collected)
+NPOW_TOO_LATE = 4  # npow_retarget, npow_relax: the search was already decided or cancelled (not yet collected)
 NPOW_ERR_NOT_INITIALISED = -1
 NPOW_ERR_NO_DEVICE = -2
 NPOW_ERR_BAD_ARGUMENT = -3
@@ -33,6 +33,7 @@ NPOW_ERR_CAPACITY = -6
 NPOW_ERR_INTERNAL = -7
 
 NPOW_ABI_VERSION = 7
+NPOW_RESERVE_MIN = 0xfffff00000000000  # the lowest reserve threshold (npow_submit_reserve)
 # hash paths of npow_values_path
 NPOW_PATH_SEARCH = 0   # the stream the search and sweep kernels execute (four 512-lane workgroups per CU)
 NPOW_PATH_SEQ = 1      # a second generated stream, scheduled without barriers
@@ -49,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "npow_set_pool_tuning", "npow_values_path", "npow_wait_info", "npow_device_stats_get_sized",
     "npow_abi_version", "npow_config_cpu_threads", "npow_wait_result", "npow_submit_weighted",
     "npow_promote", "npow_retarget", "npow_submit_background", "npow_ticket_background",
+    "npow_submit_reserve", "npow_ticket_reserve", "npow_relax",
 )
 
 
@@ -119,6 +121,22 @@ class SearchInfo(ctypes.Structure):
         ("retargets", ctypes.c_uint64),           # ABI 7, with npow_retarget
         ("stale_hits", ctypes.c_uint64),
         ("stale_wins", ctypes.c_uint64),
+    ]
+
+
+class ReserveInfo(ctypes.Structure):
+    """npow_reserve_info: the reserve of a search submitted with a reserve threshold (npow_ticket_reserve)."""
+    _fields_ = [
+        ("size", ctypes.c_uint32),
+        ("armed", ctypes.c_uint32),
+        ("reserve_threshold", ctypes.c_uint64),
+        ("threshold", ctypes.c_uint64),
+        ("nonce", ctypes.c_uint64),
+        ("value", ctypes.c_uint64),
+        ("device", ctypes.c_int32),
+        ("answered", ctypes.c_uint32),
+        ("relaxes", ctypes.c_uint64),
+        ("candidates", ctypes.c_uint64),
     ]
 
 
@@ -224,6 +242,13 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.npow_submit_background.restype = ctypes.c_int
             lib.npow_ticket_background.argtypes = [u64, ctypes.POINTER(ctypes.c_uint32)]
             lib.npow_ticket_background.restype = ctypes.c_int
+        if hasattr(lib, "npow_submit_reserve"):  # added within ABI 7: probed for
+            lib.npow_submit_reserve.argtypes = [u8p, u64, u64, u64, u64, p, u32, u32, pu64]
+            lib.npow_submit_reserve.restype = ctypes.c_int
+            lib.npow_ticket_reserve.argtypes = [u64, ctypes.POINTER(ReserveInfo)]
+            lib.npow_ticket_reserve.restype = ctypes.c_int
+            lib.npow_relax.argtypes = [u64, u64, ctypes.POINTER(ctypes.c_uint32)]
+            lib.npow_relax.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -376,6 +401,44 @@ class Ticket:
             raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
         return _check(lib.npow_retarget(self.ticket, threshold), lib, ok=(NPOW_OK, NPOW_TOO_LATE)) == NPOW_OK
 
+    def reserve_info(self) -> ReserveInfo:
+        """The search's reserve as npow_ticket_reserve reports it (a look: the search is not disturbed).
+        NanoPowError(NPOW_ERR_BAD_ARGUMENT) for a collected ticket -- and when the loaded library has no
+        npow_ticket_reserve."""
+        lib = self.engine.lib
+        if not hasattr(lib, "npow_ticket_reserve"):
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_ticket_reserve")
+        if self.result is not None:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
+        info = ReserveInfo()
+        info.size = ctypes.sizeof(ReserveInfo)
+        _check(lib.npow_ticket_reserve(self.ticket, ctypes.byref(info)), lib)
+        return info
+
+    def reserve(self) -> Optional[SearchResult]:
+        """The best nonce the search has passed whose value is at or above its reserve threshold but below its
+        threshold (submit(reserve=...)), validated on the CPU; None while there is none.  nonces_done is 0."""
+        info = self.reserve_info()
+        return SearchResult(NPOW_OK, info.nonce, info.value, 0) if info.value else None
+
+    def relax(self, threshold: int) -> Optional[bool]:
+        """Lower the search's threshold to min(current, threshold) in place (npow_relax; a search submitted with a
+        reserve threshold, down to that threshold).  True when the search was decided at once from its reserve --
+        wait_result() then returns without waiting -- False when the threshold was lowered inside the running search
+        or nothing changed, None when it came too late (NPOW_TOO_LATE: the search was already decided or cancelled).
+        NanoPowError(NPOW_ERR_BAD_ARGUMENT) for a threshold outside 64 bits or below the reserve threshold, a search
+        without a reserve, a collected ticket -- and when the loaded library has no npow_relax."""
+        lib = self.engine.lib
+        if not hasattr(lib, "npow_relax"):
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_relax")
+        if not isinstance(threshold, int) or isinstance(threshold, bool) or not 0 <= threshold <= M64:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "threshold must be an integer in [0, 2^64)")
+        if self.result is not None:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
+        answered = ctypes.c_uint32(0)
+        rc = _check(lib.npow_relax(self.ticket, threshold, ctypes.byref(answered)), lib, ok=(NPOW_OK, NPOW_TOO_LATE))
+        return None if rc == NPOW_TOO_LATE else bool(answered.value)
+
     def __del__(self) -> None:
         # An abandoned ticket: cancel its search and collect it, so the engine forgets the job
         # and stops reading this ticket's cancel word before that word is freed.  A job that
@@ -432,15 +495,35 @@ class Engine:
     # -- work pool: asynchronous searches ---------------------------------------------------
     def submit(self, root: bytes, threshold: int, start: int = 0, device_mask: int = 0,
                max_nonces_per_device: int = 0, cancel: Optional[CancelToken] = None, weight: int = 1,
-               background: bool = False) -> "Ticket":
+               background: bool = False, reserve: Optional[int] = None) -> "Ticket":
         """Queue a first-win search and return at once (npow_submit_weighted).  Keep `cancel` alive
         until the ticket's result has been collected (the Ticket holds a reference).
         weight (1, 2, 4 or 8): the search's share of each GPU among the live unbounded searches, weight /
         (sum of weights), and its place among the jobs waiting for admission (heaviest first).
         background=True (npow_submit_background; unbounded, weight 1): the search hashes only on workgroups no
         foreground search wants, until Ticket.promote lifts it.  NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the loaded
-        library has no npow_submit_background, and with max_nonces_per_device or a weight other than 1."""
+        library has no npow_submit_background, and with max_nonces_per_device or a weight other than 1.
+        reserve (npow_submit_reserve; unbounded): a reserve threshold in [NPOW_RESERVE_MIN, threshold] -- the search
+        remembers the best nonce it passes whose value is at or above it (Ticket.reserve) and can be lowered to any
+        level down to it while it runs (Ticket.relax).  NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the loaded library
+        has no npow_submit_reserve, and with max_nonces_per_device."""
         t = ctypes.c_uint64(0)
+        if reserve is not None:
+            if not hasattr(self.lib, "npow_submit_reserve"):
+                raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_submit_reserve")
+            if not isinstance(reserve, int) or isinstance(reserve, bool) or not 0 <= reserve <= M64:
+                raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "reserve must be an integer in [0, 2^64)")
+            if not isinstance(weight, int) or isinstance(weight, bool) or not 0 <= weight <= 0xffffffff:
+                raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "weight must be 1, 2, 4 or 8")
+            if max_nonces_per_device or (background and weight != 1):
+                raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "a search with a reserve is unbounded (and a background "
+                                                          "one has weight 1)")
+            _check(self.lib.npow_submit_reserve(_root(root), threshold & M64, reserve, start & M64, device_mask,
+                                                cancel.address if cancel else None, weight, 1 if background else 0,
+                                                ctypes.byref(t)), self.lib)
+            tk = Ticket(self, t.value, cancel)
+            tk.submitted_background = bool(background)
+            return tk
         if background:
             if not hasattr(self.lib, "npow_submit_background"):
                 raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_submit_background")

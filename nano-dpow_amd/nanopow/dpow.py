@@ -41,6 +41,13 @@ with a ``work_promote`` beside it when the type is heavier too.  The handler rec
 difficulty; a reply whose ``difficulty`` is below it means the raise came too late, and the hash
 is queued again at the recorded difficulty instead of being published.  Without the option such
 a message is ignored as before.
+
+Relaxing, opt-in (``relax=True``), the other direction: a precache search runs at the send
+difficulty and the block turns out to be a receive, 64 times easier.  A message for a known hash
+at a LOWER difficulty then lowers a queued hash's difficulty, and for an ongoing hash is passed to
+the work server as ``work_relax`` (nanopow.server: a search with a reserve is decided at once from
+the best nonce it has passed, or goes on in place at the lower difficulty); the handler records
+the new difficulty.  A heavier type promotes as above.  Without the option the difficulty stays.
 """
 from __future__ import annotations
 
@@ -161,7 +168,7 @@ class DpowWorkHandler:
 
     def __init__(self, worker: HttpWorker, publish: PublishFn, payout: str, concurrency: int = 1,
                  rng: Optional[random.Random] = None, weights: Optional[Dict[str, int]] = None,
-                 retarget: bool = False, background_types: Tuple[str, ...] = ()) -> None:
+                 retarget: bool = False, background_types: Tuple[str, ...] = (), relax: bool = False) -> None:
         # background_types (opt-in, e.g. ("precache",)): requests of these work types are sent with
         # "background": true -- they hash only on what no other search wants -- and rank below every other type, so
         # the same hash again under any other type (work/ondemand) promotes the search, queued or ongoing
@@ -171,6 +178,7 @@ class DpowWorkHandler:
             if w not in (1, 2, 4, 8):
                 raise ValueError(f"weight of work type {t!r} must be 1, 2, 4 or 8, not {w!r}")
         self.retarget = retarget
+        self.relax = relax
         self.worker = worker
         self.publish = publish
         self.payout = payout
@@ -181,7 +189,7 @@ class DpowWorkHandler:
         self._ready = asyncio.Event()
         self._tasks = []
         self.stats = {"queued": 0, "ignored": 0, "sent": 0, "cancelled": 0, "errors": 0, "promoted": 0,
-                      "retargeted": 0, "requeued": 0}
+                      "retargeted": 0, "requeued": 0, "relaxed": 0}
 
     async def start(self) -> None:
         # WorkHandler.start: the probe must answer with an "error" field (work_handler.py:53)
@@ -223,6 +231,11 @@ class DpowWorkHandler:
             if self.retarget and _difficulty_above(difficulty, old_difficulty):
                 await self._retarget(block_hash, queued, work_type, difficulty)
                 return
+            if self.relax and _difficulty_above(old_difficulty, difficulty):
+                await self._relax(block_hash, queued, difficulty)
+                old_difficulty = difficulty
+                if self._rank(work_type) <= self._rank(old_type):
+                    return  # (a heavier type also promotes, below)
             if self._rank(work_type) <= self._rank(old_type) or not _difficulty_not_above(difficulty, old_difficulty):
                 self.stats["ignored"] += 1
                 return
@@ -260,6 +273,18 @@ class DpowWorkHandler:
                 await self.worker.post({"action": "work_promote", "hash": block_hash, "weight": weight})
         except Exception as e:  # noqa: BLE001 -- a reply below the recorded difficulty is queued again
             log.error("Work handler retarget error: %s", e)
+
+    async def _relax(self, block_hash: str, queued: bool, difficulty: str) -> None:
+        """The same hash again at a lower difficulty (module docstring; ``relax=True``)."""
+        self.stats["relaxed"] += 1
+        if queued:
+            self.queue[block_hash] = (difficulty, self.queue[block_hash][1])
+            return
+        self.ongoing[block_hash][0] = difficulty
+        try:
+            await self.worker.post({"action": "work_relax", "hash": block_hash, "difficulty": difficulty})
+        except Exception as e:  # noqa: BLE001 -- the search goes on at its old difficulty: its result still serves
+            log.error("Work handler relax error: %s", e)
 
     async def queue_cancel(self, block_hash: str) -> None:
         if self.queue.pop(block_hash, None) is not None:

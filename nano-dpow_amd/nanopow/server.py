@@ -43,6 +43,16 @@ search hashes only on the GPU workgroups no foreground search wants
 A later foreground ``work_generate`` for the same hash and difficulty, or a
 ``work_promote`` for the hash, lifts it to a foreground search of that weight, also
 while it runs.  ``status`` reports how many searches in flight are background.
+With ``--reserve-difficulty HEX`` (``WorkServer(reserve_threshold=...)``; off by default, and a request's
+``"reserve": "<hex>"`` -- this server's extension -- sets it for that request) every
+``work_generate`` above that difficulty is searched with it as its reserve threshold
+(npow_submit_reserve): the search remembers the best nonce it passes that meets the reserve
+difficulty.  A ``work_generate`` for the same hash at a lower difficulty is then answered at
+once from that reserve when it qualifies, while the harder search runs on for the waiters that
+asked for more (the server never lowers a shared search by itself), and
+``{"action": "work_relax", "hash": ..., "difficulty": ...}`` (or ``"multiplier"``; answered
+``{}`` like ``work_retarget``) lowers every queued or running search of the hash that is above
+it, in place (npow_relax: decided at once from its reserve when that qualifies).
 The reference serves one request at a time; here up to ``max_active`` queued
 requests are handed to libnanopow's work pool at once (npow_submit), where
 every selected GPU searches all of them in the same kernel launches, so a
@@ -67,7 +77,7 @@ import time
 from typing import Any, Dict, List, Optional, Protocol
 
 from . import work as W
-from ._lib import NPOW_CANCELLED, NPOW_OK, CancelToken, NanoPowError, SearchResult
+from ._lib import NPOW_CANCELLED, NPOW_OK, NPOW_RESERVE_MIN, CancelToken, NanoPowError, SearchResult
 
 log = logging.getLogger("nanopow.server")
 
@@ -84,18 +94,21 @@ class SearchEngine(Protocol):
     def submit(self, root: bytes, threshold: int, start: int = 0, device_mask: int = 0,
                max_nonces_per_device: int = 0, cancel: Optional[CancelToken] = None) -> SearchTicket: ...
     # (an engine that serves weighted requests also takes `weight: int = 1`; passed only when it is not 1 -- and one
-    # that serves background requests `background: bool = False`; passed only when it is set)
+    # that serves background requests `background: bool = False`; passed only when it is set -- and one that keeps
+    # reserves `reserve: Optional[int] = None`; passed only for a request with a reserve difficulty)
 
     def work_value(self, root: bytes, nonce: int) -> int: ...
 
 
 class Job:
     __slots__ = ("root", "threshold", "cancel", "done", "reply", "active", "t_queued", "waiters", "t_started",
-                 "ticket", "dispatched", "collector", "weight", "background")
+                 "ticket", "dispatched", "collector", "weight", "background", "reserve")
 
-    def __init__(self, root: bytes, threshold: int, weight: int = 1, background: bool = False) -> None:
+    def __init__(self, root: bytes, threshold: int, weight: int = 1, background: bool = False,
+                 reserve: Optional[int] = None) -> None:
         self.root = root
         self.threshold = threshold
+        self.reserve = reserve  # its reserve threshold (below `threshold` when queued), None: a search without one
         self.weight = 1 if background else weight
         self.background = background  # until a foreground duplicate or a work_promote lifts it
         self.cancel = CancelToken()
@@ -125,9 +138,13 @@ class WorkServer:
     for its own result.  A request costs no thread hand-off on the way in or out."""
 
     def __init__(self, engine: SearchEngine, base_threshold: int = W.DEFAULT_BASE, shuffle: bool = False,
-                 device_mask: int = 0, rng: Optional[random.Random] = None, max_active: int = 4) -> None:
+                 device_mask: int = 0, rng: Optional[random.Random] = None, max_active: int = 4,
+                 reserve_threshold: Optional[int] = None) -> None:
         if max_active < 1:
             raise ValueError("max_active must be >= 1")
+        if reserve_threshold is not None and not NPOW_RESERVE_MIN <= reserve_threshold <= W.M64:
+            raise ValueError(f"reserve_threshold must be at least {NPOW_RESERVE_MIN:016x}")
+        self.reserve_threshold = reserve_threshold
         self.engine = engine
         self.base = base_threshold
         self.shuffle = shuffle
@@ -209,6 +226,8 @@ class WorkServer:
                 return self.work_promote(req)
             if action == "work_retarget":
                 return self.work_retarget(req)
+            if action == "work_relax":
+                return self.work_relax(req)
             if action == "work_validate":
                 return self.work_validate(req)
             if action == "status":
@@ -224,7 +243,12 @@ class WorkServer:
         threshold = W.requested_threshold(req, self.base)
         weight = W.parse_weight(req)
         background = W.parse_background(req)
-        return self._result(self._enqueue(root, threshold, weight, background))
+        reserve = W.parse_reserve(req, NPOW_RESERVE_MIN)
+        if reserve is None:
+            reserve = self.reserve_threshold
+        if reserve is not None and reserve >= threshold:  # (at or below the reserve difficulty: a plain search)
+            reserve = None
+        return self._result(self._enqueue(root, threshold, weight, background, reserve))
 
     def work_cancel(self, req: Dict[str, Any]) -> Dict[str, Any]:
         root = W.parse_hash(req)
@@ -308,6 +332,63 @@ class WorkServer:
             with self._lock:
                 job.threshold = max(job.threshold, threshold)
 
+    def work_relax(self, req: Dict[str, Any]) -> Dict[str, Any]:
+        """Lower every queued or in-flight job of the hash that has a reserve and is above the difficulty to it (this
+        server's extension; work_retarget's mirror).  A job still waiting here, or one whose submit is under way
+        (_submit compares again once the ticket exists), only changes its field; one in the engine is relaxed there
+        (_relax, once the lock is released: decided at once from its reserve when that qualifies) and its field
+        follows.  Refused, with nothing changed, when the difficulty is below the reserve of such a job."""
+        root = W.parse_hash(req)
+        threshold = W.requested_threshold(req, self.base)
+        in_engine = []
+        with self._lock:
+            jobs = [j for j in self._inflight + self._queue
+                    if j.root == root and not j.cancel.is_set and j.reserve is not None and j.threshold > threshold]
+            if any(threshold < j.reserve for j in jobs):
+                raise W.RequestError("Bad difficulty", "Below the reserve difficulty of a search for this hash")
+            for j in jobs:
+                if j.active and j.ticket is not None:
+                    in_engine.append(j)
+                else:
+                    j.threshold = threshold
+        for j in in_engine:
+            self._relax(j, threshold)
+        log.info("Relax %s to difficulty %016x", root.hex().upper(), threshold)
+        return {}
+
+    def _relax(self, job: Job, threshold: int) -> None:
+        t = job.ticket
+        if t is None or not hasattr(t, "relax"):  # an engine without reserves keeps serving
+            return
+        try:
+            answered = t.relax(threshold)
+        except Exception as e:  # (its search ended and was collected meanwhile: nothing to lower)
+            log.debug("relax %s: %s", job.root.hex().upper(), e)
+            return
+        if answered is not None:  # (None: decided already -- its reply, at the old difficulty, is on its way)
+            with self._lock:
+                job.threshold = min(job.threshold, threshold)
+
+    def _from_reserve(self, job: Job, threshold: int) -> Optional[Dict[str, Any]]:
+        """The reply to a request at `threshold` from the reserve of the harder in-flight job, or None: a look at
+        the job's reserve (Ticket.reserve: no GPU wait), re-validated as every reply is.  The job runs on."""
+        t = job.ticket
+        if t is None or not hasattr(t, "reserve"):
+            return None
+        try:
+            res = t.reserve()
+            if res is None or res.nonce is None:
+                return None
+            value = self.engine.work_value(job.root, res.nonce)
+        except Exception as e:  # (collected meanwhile, or an engine error: serve the request as ever)
+            log.debug("reserve of %s: %s", job.root.hex().upper(), e)
+            return None
+        if value < threshold:
+            return None
+        log.info("Answered %s from a reserve for difficulty %016x", job.root.hex().upper(), threshold)
+        return {"work": W.fmt_u64(res.nonce), "difficulty": W.fmt_u64(value),
+                "multiplier": W.fmt_multiplier(W.to_multiplier(value, self.base))}
+
     def work_validate(self, req: Dict[str, Any]) -> Dict[str, Any]:
         root = W.parse_hash(req)
         nonce = W.parse_work(req)
@@ -347,7 +428,24 @@ class WorkServer:
                 "hint": "Times in milliseconds"}
 
     # -- queue -------------------------------------------------------------------------
-    def _enqueue(self, root: bytes, threshold: int, weight: int = 1, background: bool = False) -> Job:
+    def _enqueue(self, root: bytes, threshold: int, weight: int = 1, background: bool = False,
+                 reserve: Optional[int] = None) -> Job:
+        # An easier duplicate: the hash has a harder job in the engine that keeps a reserve.  A qualifying reserve
+        # answers this request at once; the harder job is left as it is -- its waiters asked for more and must not
+        # be handed less, so a shared job is never relaxed here.  No qualifying reserve: served as ever, below.
+        harder: List[Job] = []
+        with self._lock:
+            same = [j for j in self._inflight + self._queue if j.root == root and not j.cancel.is_set]
+            # (a job at this very difficulty is shared, as ever)
+            if self._running and not any(j.threshold == threshold for j in same):
+                harder = [j for j in same if j.reserve is not None and j.threshold > threshold
+                          and j.ticket is not None and not j.done.is_set()]
+        for h in harder:
+            reply = self._from_reserve(h, threshold)
+            if reply is not None:
+                j = Job(root, threshold)
+                j.resolve(reply)
+                return j
         with self._lock:
             if not self._running:
                 j = Job(root, threshold)
@@ -364,7 +462,7 @@ class WorkServer:
                     break
             else:
                 dup, promote = None, False
-                job = Job(root, threshold, weight, background)
+                job = Job(root, threshold, weight, background, reserve)
                 self._queue.append(job)
                 ready = self._pump_locked()
         if dup is not None:
@@ -404,15 +502,19 @@ class WorkServer:
                 extra = {"weight": sent} if sent != 1 else {}
                 if sent_bg:  # (likewise only when asked for)
                     extra["background"] = True
+                if job.reserve is not None and job.reserve < sent_threshold:  # (likewise)
+                    extra["reserve"] = job.reserve
                 ticket = self.engine.submit(job.root, sent_threshold, start=self.rng.getrandbits(64),
                                             device_mask=self.device_mask, cancel=job.cancel, **extra)
-                with self._lock:  # (a heavier duplicate or a work_retarget may have come while the submit was under way)
+                with self._lock:  # (a heavier duplicate, a work_retarget or a work_relax may have come while the submit was under way)
                     job.ticket = ticket
                     now, now_threshold, now_bg = job.weight, job.threshold, job.background
                 if now > sent or (sent_bg and not now_bg):
                     self._promote(job, now)
                 if now_threshold > sent_threshold:
                     self._retarget(job, now_threshold)
+                elif now_threshold < sent_threshold:  # (a work_relax came meanwhile)
+                    self._relax(job, now_threshold)
             except Exception as e:  # never leave a client waiting
                 log.error("Error computing work: %s", e)
                 self._complete(job, dict(GENERATION_FAILED))

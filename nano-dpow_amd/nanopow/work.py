@@ -21,6 +21,8 @@ RECEIVE_THRESHOLD = 0xfffffe0000000000
 # Base threshold the multiplier is quoted against (nano-work-server.exe @1681900:
 # "Configured for the live network with threshold fffffff800000000").
 DEFAULT_BASE = SEND_THRESHOLD
+# The lowest reserve difficulty (include/nanopow.h NPOW_RESERVE_MIN; --reserve-difficulty, a request's "reserve")
+RESERVE_MIN = 0xfffff00000000000
 
 SUPPORTED = "Supported commands: work_generate, work_cancel, work_validate, benchmark, status"
 
@@ -114,6 +116,21 @@ def requested_threshold(req: Dict[str, Any], base: int) -> int:
     if req.get("multiplier") is not None:
         return from_multiplier(parse_multiplier(req["multiplier"]), base)
     return base
+
+
+def parse_reserve(req: Dict[str, Any], minimum: int):
+    """The optional ``"reserve"`` of a work_generate request (16 hex digits like a difficulty; this server's
+    extension): the reserve difficulty of the request's search (npow_submit_reserve), at least `minimum`.  None when
+    absent."""
+    r = req.get("reserve")
+    if r is None:
+        return None
+    bad = RequestError("Bad reserve", f"Expecting a hex difficulty of at least {minimum:016x}")
+    if not isinstance(r, str) or not _HEX64.fullmatch(r):
+        raise bad
+    if int(r, 16) < minimum:
+        raise bad
+    return int(r, 16)
 
 
 WEIGHTS = (1, 2, 4, 8)
