@@ -399,6 +399,34 @@ int npow_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint6
                uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* out, uint64_t cap,
                uint64_t* n_out);
 
+/* Sweep jobs (added within ABI 7; probe for the symbols): the same enumeration as a job of the work pool.  npow_sweep
+ * takes each device from the pool for as long as it runs -- every search on it waits -- whereas a sweep job has a
+ * ticket and shares the pool's launches with up to 63 other jobs: it is hashed by the kernels that answer searches,
+ * a bounded job whose hits are collected instead of ending it.
+ *
+ * npow_submit_sweep returns at once.  Any threshold; [start, start + count) is taken mod 2^64 and split into contiguous
+ * parts over the GPUs of device_mask (0 = all), as npow_sweep splits it; the CPU workers take no part.  The job takes a
+ * slot like a bounded search (weight 1, foreground), counts against npow_pool_config's limit and queues like any job.
+ * count == 0 completes at once with no hits and touches no device.
+ *
+ * npow_wait_sweep alone collects such a ticket.  NPOW_PENDING when timeout_us (< 0: none) passes first; the ticket
+ * stays valid.  NPOW_OK: every nonce of the range was hashed exactly once; out[0..min(n, cap)) holds the hits in
+ * ascending (nonce - start) order, *n_out = n, the exact hit count, *nonces_done (may be null) = count.
+ * NPOW_ERR_CAPACITY: more hits than cap, or more than NPOW_SWEEP_JOB_HITS on one device; *n_out is still exact and
+ * out holds the first hits.  NPOW_CANCELLED after npow_cancel or *cancel: out holds the hits found so far, ascending,
+ * *n_out their number, *nonces_done what was hashed.  A device dropped while it holds the job fails the job with that
+ * device's error: a part of the range is never hashed again elsewhere, which would report hits twice.  A hit reported
+ * twice is NPOW_ERR_INTERNAL, never deduplicated.  Every status but NPOW_PENDING releases the ticket.
+ *
+ * npow_cancel works on a sweep job's ticket.  npow_promote, npow_retarget, npow_relax, npow_ticket_reserve,
+ * npow_ticket_background, npow_wait, npow_wait_info and npow_wait_result return NPOW_ERR_BAD_ARGUMENT and leave it
+ * collectable, as npow_wait_sweep does for a search's ticket. */
+#define NPOW_SWEEP_JOB_HITS 1048576 /* hits one device keeps for one sweep job (2^20, npow_sweep's device buffer) */
+int npow_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count,
+                      uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket);
+int npow_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t cap, uint64_t* n_out,
+                    uint64_t* nonces_done);
+
 /* Work values of `count` consecutive nonces start, start+1, ... for one root,
  * computed by the instruction stream the search and sweep kernels execute
  * (npow_values_kernel_ls2: the same uniform loads, priority runs and

@@ -799,6 +799,20 @@ int npow_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered) try {
   return rc;
 } catch (...) { return guard_exception(); }
 
+int npow_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count,
+                      uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket) try {
+  if (int rc = check_init()) return rc;
+  if (!root || !ticket) return fail(NPOW_ERR_BAD_ARGUMENT, "root and ticket are required");
+  return pool_submit_sweep(root, threshold, start, count, device_mask, cancel, ticket);
+} catch (...) { return guard_exception(); }
+
+int npow_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t cap, uint64_t* n_out,
+                    uint64_t* nonces_done) try {
+  if (int rc = check_init()) return rc;
+  if (!n_out || (cap && !out)) return fail(NPOW_ERR_BAD_ARGUMENT, "n_out (and out when cap > 0) required");
+  return pool_wait_sweep(ticket, timeout_us, out, cap, n_out, nonces_done);
+} catch (...) { return guard_exception(); }
+
 int npow_pool_config(uint32_t max_active) try {
   if (int rc = check_init()) return rc;
   return pool_set_max_active(max_active);

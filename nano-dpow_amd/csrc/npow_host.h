@@ -58,6 +58,11 @@ struct Device {
   PoolTable* h_tab[kEventRing] = {};   // pinned staging
   unsigned long long* h_done = nullptr;  // pinned read-back of every slot's done shards
   hipEvent_t ev_done[kMaxSlots] = {};    // the read-back of a retiring slot has landed
+  // sweep jobs (Worker::collect_hits): a retired launch's hit counters and one entry's records are copied on a stream
+  // of their own (non-blocking: the next launch may be running on `stream`) into these pinned buffers
+  hipStream_t hit_stream = nullptr;
+  unsigned long long* h_hit_n = nullptr;  // PoolHits::n
+  uint64_t* h_hits = nullptr;             // kSweepHits records
   std::thread worker;
   // statistics
   std::mutex stats_mu;
@@ -213,6 +218,12 @@ int pool_promote(uint64_t ticket, uint32_t weight);  // weight: 1, 2, 4 or 8 (np
 int pool_retarget(uint64_t ticket, uint64_t threshold);  // npow_retarget
 int pool_ticket_reserve(uint64_t ticket, npow_reserve_info* out);  // npow_ticket_reserve (out: a full struct)
 int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered);  // npow_relax (answered: not null)
+// sweep jobs (npow_submit_sweep, npow_wait_sweep; arguments checked by the caller)
+int pool_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count, uint64_t device_mask,
+                      const volatile uint32_t* cancel, uint64_t* ticket);
+int pool_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t cap, uint64_t* n_out,
+                    uint64_t* nonces_done);
+static_assert(NPOW_SWEEP_JOB_HITS == kSweepHits, "the published capacity is the device's record set");
 int pool_set_max_active(uint32_t n);
 void pool_counts(uint32_t* queued, uint32_t* active);
 

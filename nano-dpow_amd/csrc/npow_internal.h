@@ -111,7 +111,10 @@ struct PoolEntry {
   uint64_t count;
   uint64_t gen;
   uint32_t slot;     // device slot index (PoolDevState / PoolMailbox arrays)
-  uint32_t bounded;  // 1: dense mapping over the entry's own workgroups, no migrants
+  uint32_t bounded;  // bit 0 (kEntryBounded): dense mapping over the entry's own workgroups, no migrants.  Bit 1
+                     // (kEntryCollect, with bit 0): a sweep job's entry (npow_submit_sweep) -- it never wins, every
+                     // lane at or above the threshold is appended to the launch's hit records (PoolHits); bits 8..15:
+                     // the entry's region of the records, bits 16..20: the regions' size as a shift (pool_collect_*)
   uint32_t wsh;      // unbounded: 3 - log2(weight), weight in {1, 2, 4, 8} (npow_submit_weighted): wherever two
                      // entries' workgroup counts are compared, each is shifted left by its wsh first, so a job's
                      // share of the launch's workgroups is weight / (sum of weights).  Equal values compare as the
@@ -214,6 +217,24 @@ struct PoolExit {
   uint8_t pad[56];
 };
 constexpr int kPoolRing = 4;  // launch ring of the pool kernels (host: kEventRing)
+// Sweep jobs (npow_submit_sweep): the hit records of one launch.  Consecutive launches take the two sets in turn
+// (PoolTable::ring & 1; at most two launches are in flight), and a set's counters are zeroed in stream order before
+// the launch that uses it, after the host has read what the launch before the last left there -- no host write races
+// a running launch, and a record belongs to the generation whose entry the launch's table held in that slot.  The
+// records are dealt to the launch's collecting entries in 2^shift equal regions (PoolEntry::bounded carries the
+// entry's region and the shift): a hit lane of slot s stores its nonce at rank n[s]++ of its entry's region, or not
+// at all past the region's end -- the counter keeps counting, so the hit count stays exact.
+constexpr uint32_t kSweepHits = 1u << 20;  // records per set (NPOW_SWEEP_JOB_HITS, include/nanopow.h)
+constexpr uint32_t kEntryBounded = 1u, kEntryCollect = 2u;
+__host__ __device__ inline uint32_t pool_collect_flags(uint32_t region, uint32_t shift) {
+  return kEntryBounded | kEntryCollect | (region << 8) | (shift << 16);
+}
+__host__ __device__ inline uint32_t pool_collect_region(uint32_t bounded) { return (bounded >> 8) & 0xffu; }
+__host__ __device__ inline uint32_t pool_collect_shift(uint32_t bounded) { return (bounded >> 16) & 0x1fu; }
+struct PoolHits {
+  unsigned long long n[kMaxSlots];  // hits of the slot's entry in this launch (may exceed its region)
+  uint64_t rec[kSweepHits];         // the nonces, region by region, each in the order its waves came
+};
 struct PoolDevState {
   PoolSlotWord slot[kMaxSlots];
   PoolSlotCount count[kMaxSlots][kWgsShards];
@@ -241,6 +262,8 @@ struct PoolDevState {
   // generations only grow, so the first candidate of a new generation beats whatever the last one left: arming the
   // slot (its entry's generation, written by the host) resets the word without a write to device memory.
   alignas(64) unsigned long long reserve_best[kMaxSlots];
+  // Sweep jobs: the hit records of the launches in flight (PoolHits above; 2 x 8 MiB).  Last: nothing above moves.
+  alignas(64) PoolHits hits[2];
 };
 // The key of a reserve candidate: the slot's generation above 24 bits of the value.  Reserve thresholds are at least
 // NPOW_RESERVE_MIN (fffff00000000000), so a candidate's top 20 bits are ones and bits 43..20 order candidates to one

@@ -980,6 +980,29 @@ __device__ __noinline__ uint32_t ls2_pick(const PoolTable* tab, PoolDevState* st
   return ls2_choose(tab, st, mb, e, nd, seen, lane, g);
 }
 
+// A collecting entry's hit lanes (pool_body_ls2, BOUNDED only; PoolHits, npow_internal.h).  One atomic per wave takes
+// popcount(hits) ranks of the slot's counter in the launch's set: with threshold 0 every wave of the entry comes here
+// every iteration, and atomics on one address serialise at the memory side (~18 ns each), so one per lane would be 64
+// times that.  Each hit lane then stores its nonce at its rank of the entry's region with a plain vector store, unless
+// the rank is past the region's end -- the counter has counted it all the same, which keeps the hit count exact.  The
+// entry's slot and flags are re-read from it (up points at the entry), as the win path re-reads slot and generation.
+__device__ __forceinline__ void ls2_collect(const PoolTable* tab, PoolDevState* st, const uint64_t* up, uint64_t hits,
+                                            bool hit, uint64_t nonce, uint32_t lane) {
+  ConstEntry* ce = (ConstEntry*)(uintptr_t)up;
+  asm volatile("" : "+s"(ce));
+  const uint32_t slot = ce->slot, flags = ce->bounded;
+  const uint32_t shift = pool_collect_shift(flags), region = pool_collect_region(flags);
+  const uint32_t room = kSweepHits >> shift;
+  PoolHits* ph = &st->hits[tab->ring & 1u];
+  if (region >= (1u << shift) || slot >= (uint32_t)kMaxSlots) return;  // (never: the host's table; keeps every index in)
+  unsigned long long first = 0;
+  if (lane == 0) first = atomicAdd(&ph->n[slot], (unsigned long long)__builtin_popcountll(hits));
+  first = uni64(first);
+  const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(hits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hits, 0u));
+  const unsigned long long rank = first + below;
+  if (hit && rank < room) ph->rec[(size_t)region * room + (size_t)rank] = nonce;
+}
+
 // Odd, so that it0 -> -it0 * kPollStride is a bijection modulo every power of two; its residues mod 2^10..2^13 step
 // by 0.43, 0.22, 0.11 and 0.80 of the range (the fractional part of the golden ratio in 32 bits).
 constexpr uint32_t kPollStride = 0x9E3779B9u;
@@ -1083,6 +1106,16 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
         done += 64;
       }
       uint64_t hits = __ballot(hit);
+      // Sweep jobs (npow_submit_sweep; only bounded entries collect, so only the BOUNDED kernels carry this): a
+      // collecting entry never wins.  Its hit lanes (under the bounded lane mask above) append their nonces to the
+      // entry's region of the launch's hit records and the wave goes on with no hit left: no win record, no dead
+      // word, no stop request, no floor and no reserve.
+      if constexpr (BOUNDED) {
+        if (__builtin_expect(hits != 0, 0) && (c.bounded & kEntryCollect)) {
+          ls2_collect(tab, st, c.up, hits, hit, nonce, lane);
+          hits = 0;
+        }
+      }
       // why the workgroup must leave the entry, as a stop-request kind (0 = not at all; the time budget files
       // kind 0 = end the launch): 1 = the entry was over before this hash started (its dead word), 2 = it is
       // over since this hash (a win; a kill read by this wave's poll), 3 = leave for another reason (a yield,

@@ -24,6 +24,10 @@
 // launch as a dynamic entry (dyn_add; PoolMailbox::dyn) instead of ending it (yield_if_long, now
 // the fallback).  DESIGN.md section 1.
 //
+// A sweep job (npow_submit_sweep) is a bounded job that never wins: its entries collect every hit of their ranges in
+// the launch's hit records (PoolHits), which the worker reads as each launch retires (collect_hits); pool_wait_sweep
+// merges them.  DESIGN.md section 1 "Sweep jobs".
+//
 // Threads: one persistent worker per device (started by npow_init) owns the device's
 // stream, its slot table and up to two launches in flight (the second is queued only near
 // the end of the first one's budget, or at once behind a launch with no live entry left);
@@ -49,6 +53,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
@@ -258,6 +263,14 @@ void abandon_locked(const JobP& j, size_t k, int code, const std::string& msg) {
   if (j->dev[k].done) return;
   std::deque<Range> rest;
   rest.swap(j->dev[k].todo);
+  if (j->sweep && !j->decided) {
+    // a sweep job's part is never hashed again on another device -- the hits the dead device had reported, or was
+    // about to, would come twice: the job fails with the device's error, and its other devices stop
+    j->err = msg;
+    decide_locked(*j, code);
+    g_pool.decisions.fetch_add(1, std::memory_order_release);
+    notify_workers_locked();
+  }
   if (!j->decided && !rest.empty()) {
     // the surviving GPUs take it; the CPU device (npow_cpu.cpp) only when no GPU of the job is left
     std::vector<size_t> surv, surv_cpu;
@@ -377,7 +390,29 @@ struct PoolInflight {
   bool linger;          // PoolTable::linger: its workgroups wait for dynamic entries until its budget or a yield
   uint32_t wdown;       // its table's weights were halved this many times (pool_table_weights): its dynamic entries' too
   bool bounded;         // its table holds a bounded entry: no entry of the launch carries the background flag
+  // Its collecting entries (sweep jobs): the slot and generation of each, and its region of the launch's hit records
+  // (PoolHits; the set is ring & 1), `room` records from record region * room on.  Read when the launch retires.
+  struct Collect {
+    int slot;
+    uint64_t gen;
+    uint32_t region, room;
+  };
+  std::vector<Collect> collect;
 };
+
+// The most nonces a collecting entry of threshold `threshold` takes in one launch, so that its hits fit the `room`
+// records of its region.  A launch's hits past its region are counted but not stored, and which ones are lost is up to
+// the order its waves came in -- the job would keep its exact count but not its first hits.  The number of hits in
+// `span` nonces is binomial with p = (2^64 - threshold) / 2^64: mean p * span and variance below the mean, so a span
+// with mean + 8 sigma <= room (sigma <= sqrt(room)) overflows about once in 10^15 launches; with threshold 0 every
+// nonce is a hit and the span is exact.  At the thresholds audits run with (p <= 2^-16) this is above every launch's
+// span, and the bounded jobs' own span (PoolShape::own) is what a launch takes.
+uint64_t collect_span(uint64_t threshold, uint32_t room) {
+  const double p = threshold ? (double)(0 - threshold) / 18446744073709551616.0 : 1.0;
+  const double fit = (double)room - 8.0 * std::sqrt((double)room) - 64.0;
+  const double span = (fit > 64.0 ? fit : 64.0) / p;
+  return span >= 9.0e18 ? ~0ull : (uint64_t)span;
+}
 
 class Worker {
  public:
@@ -388,6 +423,7 @@ class Worker {
   Device& d_;
   Slot slots_[kMaxSlots];
   std::deque<PoolInflight> q_;
+  std::vector<PoolInflight::Collect> collect_;  // build_table: the collecting entries of the table it built
   uint64_t seq_ = 0;  // launches issued by this worker
   uint64_t retired_seq_ = 0;  // the last launch retire_launches() has dropped (launches retire in order)
   uint64_t seen_version_ = ~0ull;
@@ -508,6 +544,7 @@ class Worker {
   void build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded);
   int launch(bool empty_linger = false);
   int queue_readbacks();
+  int collect_hits(const PoolInflight& f);
   int retire_launches();
   int retire_slots();
   int retire() {
@@ -852,6 +889,8 @@ void Worker::early_finish(int s) {
     stat([&] { d_.linger_relays++; });
   if (sl.stale) stale_fin_came(s, j.gpu_t_win);
   if (d_.dead || sl.requeue || !j.decided.load()) return;
+  if (j.sweep) return;  // a cancelled sweep job: the hits of the launches that held it are read as they retire
+                        // (collect_hits), so the slot goes the read-back's way (retire_slots)
   sl.early = true;
   credit_job_locked(sl, credit_counts(sl, total, late, stale_hits));  // retire_slots() then reads back the same total
   if (g_trace_lat && j.t_kend == 0) j.t_kend = now_us();
@@ -949,10 +988,27 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
     t.promo_base = (uint32_t)(__atomic_load_n(&d_.pmb->kills, __ATOMIC_ACQUIRE) >> 32);
     const double t_issue = now_us();
     const uint64_t full = sh.full(iters);
+    // the table's collecting entries (sweep jobs) share the launch's hit records in 2^cshift equal regions
+    uint32_t ncollect = 0, cshift = 0;
+    for (uint32_t e = 0; e < n; ++e) ncollect += slots_[idx[e]].job->sweep ? 1u : 0u;
+    while ((1u << cshift) < ncollect) ++cshift;
+    collect_.clear();
     for (uint32_t e = 0; e < n; ++e) {
       Slot& sl = slots_[idx[e]];
       const Job& j = *sl.job;
       const std::deque<Range>& todo = j.dev[sl.k].todo;
+      if (j.sweep) {
+        // the span a bounded job takes, unless the threshold is so low that its hits would not fit the region
+        const uint32_t room = kSweepHits >> cshift, region = (uint32_t)collect_.size();
+        take_entry(sl, t.e[e], std::min(sh.own(e, n, iters), collect_span(j.threshold, room)), seq_, t_issue);
+        t.e[e].bounded = pool_collect_flags(region, cshift);
+        t.e[e].wsh = pool_wsh(j.weight);
+        weights[e] = j.weight;
+        bgs[e] = 0;
+        *bounded = true;
+        collect_.push_back({idx[e], sl.gen, region, room});
+        continue;
+      }
       // the next part of the device's queue of ranges: a bounded job's own waves cover it
       // densely; an unbounded job claims a full launch region (W * iters * 64, holes allowed)
       // unless less than that is left, which then becomes a dense bounded entry too
@@ -1023,6 +1079,10 @@ int Worker::launch(bool empty_linger) {
   // competes with the running launch.)
   if (faults().hip_dev == d_.id && seq_ > faults().hip_after)  // NANOPOW_FAULT_HIP (tests)
     return fail(NPOW_ERR_HIP, "injected launch failure (NANOPOW_FAULT_HIP)");
+  // Sweep jobs: this launch's set of hit records (PoolHits) starts from zero counts, in stream order.  Its previous
+  // user, the launch before the last, has retired -- at most two are in flight -- and its hits were read then.
+  if (!collect_.empty())
+    HIPTRY(hipMemsetAsync(d_.pst->hits[r & 1].n, 0, sizeof(d_.pst->hits[r & 1].n), d_.stream));
   if (n <= (uint32_t)kArgEntries) {
     HIPTRY(hipEventRecord(d_.ev_start[r], d_.stream));
     HIPTRY(launch_pool_arg(d_.stream, sh.grid, t, bounded, d_.pst, d_.pmb_dev));
@@ -1037,7 +1097,7 @@ int Worker::launch(bool empty_linger) {
             (unsigned long long)seq_, n, t.linger, t.wsum, t.wdown, (unsigned long long)t.yield_base);
   for (uint32_t e = 0; e < n; ++e) NPOW_DBG(" %d/g%llu", idx[e], (unsigned long long)t.e[e].gen);
   NPOW_DBG("\n");
-  q_.push_back({seq_, r, (uint32_t)ctl_, t.yield_base, t.counted != 0, t.linger != 0, t.wdown, bounded});
+  q_.push_back({seq_, r, (uint32_t)ctl_, t.yield_base, t.counted != 0, t.linger != 0, t.wdown, bounded, collect_});
   publish_counted();
   return NPOW_OK;
 }
@@ -1102,6 +1162,40 @@ void Worker::trace_nofin(int s, uint64_t seq) const {
           (unsigned long long)__atomic_load_n(&d_.pmb->fin[s].gen, __ATOMIC_ACQUIRE));
 }
 
+// Launch f has completed: the hits of its collecting entries (sweep jobs) go to their jobs.  The set's counters, then
+// each entry's records up to its count or its region's end, are copied on the device's copy stream (not the launch
+// stream: the next launch may be running on it) into pinned memory; the launch after next, which zeroes this set
+// again, is issued only after this returns.  A count above the region means records were lost (JobDev::hits_lost;
+// collect_span makes that a once-in-10^15 event); the job keeps its first NPOW_SWEEP_JOB_HITS hits per device, in
+// ascending order -- a device's launches take its part's ranges in that order -- and counts them all.
+int Worker::collect_hits(const PoolInflight& f) {
+  if (f.collect.empty()) return NPOW_OK;
+  DEVCHECK(d_, "pool hit read-back");
+  PoolHits* set = &d_.pst->hits[f.ring & 1];
+  HIPTRY(hipMemcpyAsync(d_.h_hit_n, set->n, sizeof(set->n), hipMemcpyDeviceToHost, d_.hit_stream));
+  HIPTRY(hipStreamSynchronize(d_.hit_stream));
+  for (const PoolInflight::Collect& c : f.collect) {
+    Slot& sl = slots_[c.slot];
+    if (sl.state == SlotState::kFree || sl.gen != c.gen) continue;  // (a slot keeps its job while a launch holds it)
+    const uint64_t n = d_.h_hit_n[c.slot];
+    const uint64_t stored = std::min<uint64_t>(n, c.room);
+    if (stored) {
+      HIPTRY(hipMemcpyAsync(d_.h_hits, set->rec + (size_t)c.region * c.room, stored * sizeof(uint64_t),
+                            hipMemcpyDeviceToHost, d_.hit_stream));
+      HIPTRY(hipStreamSynchronize(d_.hit_stream));
+    }
+    const uint64_t start = sl.job->start;
+    std::sort(d_.h_hits, d_.h_hits + stored, [start](uint64_t x, uint64_t y) { return x - start < y - start; });
+    std::lock_guard<std::mutex> g(g_pool.mu);
+    JobDev& jd = sl.job->dev[sl.k];
+    jd.hit_n += n;
+    if (n > stored) jd.hits_lost = true;
+    const uint64_t take = std::min<uint64_t>(stored, (uint64_t)NPOW_SWEEP_JOB_HITS - jd.hits.size());
+    jd.hits.insert(jd.hits.end(), d_.h_hits, d_.h_hits + take);
+  }
+  return NPOW_OK;
+}
+
 // The launches that have completed, in order: their statistics, and the ranges they held leave the slots' inflight.
 int Worker::retire_launches() {
   while (!q_.empty()) {
@@ -1121,6 +1215,7 @@ int Worker::retire_launches() {
     uint64_t g0 = 0, g1 = 0;
     account_clock(f.ring, f.seq, &g0, &g1);
     if (g_trace_lat && g0) trace_launch(f, g0, g1);
+    if (int rc = collect_hits(f)) return rc;  // sweep jobs: before their slots can retire (retire_slots)
     // The launch's ranges are complete, except those of a generation that won in it (or in an
     // earlier launch still unseen): handle such wins first, they hand back what did not finish.
     for (int s = 0; s < kMaxSlots; ++s) {
@@ -1175,6 +1270,9 @@ int Worker::retire_slots() {
       continue;
     }
     if (sl.state != SlotState::kDraining || !sl.readback) continue;
+    // a sweep job's slot retires only after retire_launches() has read the hits of every launch that held it (the
+    // read-back's event may fire between that call's look at the launch's event and this one)
+    if (sl.job->sweep && !sl.inflight.empty()) continue;
     const hipError_t e = hipEventQuery(d_.ev_done[s]);
     if (e == hipErrorNotReady) continue;
     if (e != hipSuccess) return fail(NPOW_ERR_HIP, std::string("pool read-back: ") + hipGetErrorString(e));
@@ -1461,6 +1559,13 @@ int pool_device_init(Device& d) {
   HIPTRY(hipHostMalloc(&hd, (size_t)kMaxSlots * kPoolDoneShards * 8 * sizeof(unsigned long long), hipHostMallocDefault));
   d.h_done = (unsigned long long*)hd;
   for (int s = 0; s < kMaxSlots; ++s) HIPTRY(hipEventCreateWithFlags(&d.ev_done[s], hipEventDisableTiming));
+  // sweep jobs: the copy stream and the pinned staging of a launch's hits (8 MiB; the records themselves are the
+  // last 16 MiB of PoolDevState)
+  HIPTRY(hipStreamCreateWithFlags(&d.hit_stream, hipStreamNonBlocking));
+  void* hn = nullptr;
+  HIPTRY(hipHostMalloc(&hn, sizeof(PoolHits::n) + (size_t)kSweepHits * sizeof(uint64_t), hipHostMallocDefault));
+  d.h_hit_n = (unsigned long long*)hn;
+  d.h_hits = (uint64_t*)((char*)hn + sizeof(PoolHits::n));
   return NPOW_OK;
 }
 
@@ -1474,6 +1579,8 @@ void pool_device_free(Device& d) {  // tolerates a partial pool_device_init
   if (d.h_done) (void)hipHostFree(d.h_done);
   for (int s = 0; s < kMaxSlots; ++s)
     if (d.ev_done[s]) (void)hipEventDestroy(d.ev_done[s]);
+  if (d.h_hit_n) (void)hipHostFree(d.h_hit_n);  // (h_hits is part of it)
+  if (d.hit_stream) (void)hipStreamDestroy(d.hit_stream);
 }
 
 void pool_start() {
@@ -1647,6 +1754,13 @@ static JobP find_ticket(uint64_t ticket) {
   return it == g_pool.tickets.end() ? nullptr : it->second;
 }
 
+// A sweep job's ticket (npow_submit_sweep) is collected by pool_wait_sweep and cancelled by pool_cancel; every other
+// call on it is refused and leaves it as it was (Job::sweep does not change after the submit: no lock needed).
+static int refuse_sweep(const Job& j, const char* call) {
+  if (!j.sweep) return NPOW_OK;
+  return fail(NPOW_ERR_BAD_ARGUMENT, std::string(call) + ": the ticket is a sweep job's (npow_wait_sweep collects it)");
+}
+
 // A decided job's outcome as pool_wait and pool_wait_result return it.
 static int outcome(const Job& j, uint64_t* nonce, uint64_t* value) {
   const int st = j.status;
@@ -1661,6 +1775,7 @@ int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* va
               npow_search_info* info) {
   JobP j = find_ticket(ticket);
   if (!j) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  if (int rc = refuse_sweep(*j, "npow_wait")) return rc;
   if (wait_job(j, timeout_us, [&] { return j->finished.load(std::memory_order_acquire); }) == NPOW_PENDING)
     return NPOW_PENDING;
   std::unique_lock<std::mutex> lk(g_pool.mu);
@@ -1725,6 +1840,7 @@ int pool_wait(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* va
 int pool_wait_result(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* value) {
   JobP j = find_ticket(ticket);
   if (!j) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  if (int rc = refuse_sweep(*j, "npow_wait_result")) return rc;
   if (wait_job(
           j, timeout_us,
           [&] { return j->decided.load(std::memory_order_acquire) || j->finished.load(std::memory_order_acquire); },
@@ -1737,6 +1853,7 @@ int pool_ticket_background(uint64_t ticket, uint32_t* background) {
   std::lock_guard<std::mutex> g(g_pool.mu);
   auto it = g_pool.tickets.find(ticket);
   if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  if (int rc = refuse_sweep(*it->second, "npow_ticket_background")) return rc;
   *background = it->second->background ? 1u : 0u;
   return NPOW_OK;
 }
@@ -1767,6 +1884,7 @@ int pool_promote(uint64_t ticket, uint32_t weight) {
   auto it = g_pool.tickets.find(ticket);
   if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
   const JobP& j = it->second;
+  if (int rc = refuse_sweep(*j, "npow_promote")) return rc;
   if (weight > 1 && j->max_per_dev)
     return fail(NPOW_ERR_BAD_ARGUMENT, "a bounded search (max_nonces_per_device) takes weight 1 only");
   // A background job becomes a foreground job of this weight, whatever the weight: the same steps.  (Admitted, it
@@ -1811,6 +1929,7 @@ int pool_retarget(uint64_t ticket, uint64_t threshold) {
   auto it = g_pool.tickets.find(ticket);
   if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
   const JobP& j = it->second;
+  if (int rc = refuse_sweep(*j, "npow_retarget")) return rc;
   if (threshold <= j->threshold.load(std::memory_order_relaxed)) return NPOW_OK;  // never lowered
   if (j->finished || j->decided || j->cancel_seen()) return NPOW_TOO_LATE;        // its outcome stands
   j->threshold.store(threshold, std::memory_order_release);
@@ -1866,6 +1985,7 @@ int pool_ticket_reserve(uint64_t ticket, npow_reserve_info* out) {
   auto it = g_pool.tickets.find(ticket);
   if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
   Job& j = *it->second;
+  if (int rc = refuse_sweep(j, "npow_ticket_reserve")) return rc;
   if (j.armed && !j.decided && !j.finished) pool_harvest_locked(j);
   out->armed = j.armed ? 1u : 0u;
   out->reserve_threshold = j.reserve;
@@ -1893,6 +2013,7 @@ int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered) {
   auto it = g_pool.tickets.find(ticket);
   if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
   j = it->second;
+  if (int rc = refuse_sweep(*j, "npow_relax")) return rc;
   if (!j->armed) return fail(NPOW_ERR_BAD_ARGUMENT, "the search was submitted without a reserve threshold");
   if (threshold < j->reserve) return fail(NPOW_ERR_BAD_ARGUMENT, "below the search's reserve threshold");
   if (j->finished || j->decided || j->cancel_seen()) return NPOW_TOO_LATE;  // its outcome stands
@@ -1911,6 +2032,101 @@ int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered) {
     pool_answer_locked(*j);
     *answered = 1;
   }
+  return NPOW_OK;
+}
+
+// -- sweep jobs (npow_submit_sweep, npow_wait_sweep) ----------------------------------------------------------------
+// Every hit of [start, start + count) as a pool job: a bounded job of weight 1 and foreground class whose entries
+// collect (PoolEntry::bounded kEntryCollect) instead of winning.  The range is split into contiguous parts over the
+// GPUs of the mask, as npow_sweep splits it (a GPU whose part would be empty is left out); each worker reads its
+// launches' hits as they retire (collect_hits), and pool_wait_sweep merges the devices' lists.
+int pool_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count, uint64_t device_mask,
+                      const volatile uint32_t* cancel, uint64_t* ticket) {
+  auto j = std::make_shared<Job>();
+  j->sweep = true;
+  j->count = count;
+  j->pre = host_precompute(root);
+  npow_asm_uniforms(j->pre.m, j->u);
+  j->threshold = threshold;
+  j->reserve = threshold;
+  j->start = start;
+  j->cancel = cancel;
+  j->t_submit = now_us();
+  if (count) {
+    auto devs = select_gpus(device_mask);
+    if (devs.empty()) return fail(NPOW_ERR_NO_DEVICE, "no usable GPU in device_mask");
+    const uint64_t G = std::min<uint64_t>(devs.size(), count);
+    const uint64_t per = count / G, rem = count % G;
+    j->dev.resize(G);
+    uint64_t off = 0;
+    for (uint64_t k = 0; k < G; ++k) {
+      const uint64_t part = per + (k < rem ? 1 : 0);
+      j->devs.push_back(devs[k]->id);
+      j->dev[k].todo.push_back({start + off, part});
+      j->max_per_dev = std::max(j->max_per_dev, part);
+      off += part;
+    }
+    j->pending_devs = (int)G;
+    j->spin_us = spin_window_us(*j);
+  } else {  // nothing to hash: complete at once, no device is touched
+    j->status = NPOW_EXHAUSTED;
+    j->decided = true;
+    j->admitted = true;
+    j->t_finish = j->t_submit;
+    j->finished = true;
+  }
+  std::lock_guard<std::mutex> g(g_pool.mu);
+  if (!g_pool.running) return fail(NPOW_ERR_NOT_INITIALISED, "engine is shut down");
+  j->ticket = g_pool.next_ticket++;
+  g_pool.tickets[j->ticket] = j;
+  if (count) {
+    auto at = g_pool.waiting.end();  // its place in the queue: a foreground job of weight 1 (pool_submit)
+    while (at != g_pool.waiting.begin() && queue_rank(**(at - 1)) < queue_rank(*j)) --at;
+    g_pool.waiting.insert(at, j);
+    admit_locked();
+  }
+  *ticket = j->ticket;
+  return NPOW_OK;
+}
+
+int pool_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t cap, uint64_t* n_out,
+                    uint64_t* nonces_done) {
+  JobP j = find_ticket(ticket);
+  if (!j) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  if (!j->sweep) return fail(NPOW_ERR_BAD_ARGUMENT, "npow_wait_sweep: the ticket is a search's (npow_wait collects it)");
+  if (wait_job(j, timeout_us, [&] { return j->finished.load(std::memory_order_acquire); }) == NPOW_PENDING)
+    return NPOW_PENDING;
+  std::unique_lock<std::mutex> lk(g_pool.mu);
+  g_pool.tickets.erase(ticket);
+  uint64_t total = 0;
+  bool lost = false;
+  std::vector<uint64_t> all;
+  for (const JobDev& jd : j->dev) {
+    total += jd.hit_n;
+    lost = lost || jd.hits_lost || jd.hit_n > jd.hits.size();
+    all.insert(all.end(), jd.hits.begin(), jd.hits.end());
+  }
+  const uint64_t done = j->done;
+  const int st = j->status;
+  lk.unlock();
+  const uint64_t start = j->start;
+  std::sort(all.begin(), all.end(), [start](uint64_t x, uint64_t y) { return x - start < y - start; });
+  const uint64_t k = std::min<uint64_t>(all.size(), cap);
+  if (k) memcpy(out, all.data(), k * sizeof(uint64_t));
+  *n_out = total;
+  if (nonces_done) *nonces_done = done;
+  // every nonce is hashed once, so a nonce reported twice -- or one outside the range -- is a coverage bug: never
+  // deduplicated, the job fails
+  for (size_t i = 0; i < all.size(); ++i)
+    if (all[i] - start >= j->count || (i && all[i] == all[i - 1]))
+      return fail(NPOW_ERR_INTERNAL, "sweep job: a hit outside the range or reported twice (nonce coverage)");
+  if (st == NPOW_CANCELLED) return NPOW_CANCELLED;
+  if (st < 0) return fail(st, j->err.empty() ? std::string("sweep job failed") : j->err);
+  if (done != j->count)
+    return fail(NPOW_ERR_INTERNAL, "sweep job: hashed " + std::to_string(done) + " nonces of " + std::to_string(j->count));
+  if (lost)
+    return fail(NPOW_ERR_CAPACITY, "more than NPOW_SWEEP_JOB_HITS hits on a device (n_out is exact)");
+  if (total > cap) return fail(NPOW_ERR_CAPACITY, "more hits than cap");
   return NPOW_OK;
 }
 

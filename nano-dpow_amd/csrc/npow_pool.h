@@ -41,6 +41,12 @@ struct JobDev {
   double t_launch = 0;     // when its first launch holding the job was issued (us; 0 = none)
   uint64_t late = 0;       // nonces its waves hashed after they knew the job was over (device-side count,
                            // PoolDevState kLateWord)
+  // A sweep job's hits on this device (Worker::collect_hits, as each launch that held its entry retires): the
+  // nonces, ascending by (nonce - Job::start), at most NPOW_SWEEP_JOB_HITS of them -- the first ones, while no
+  // launch's records overflowed (hits_lost) -- and their exact number.
+  std::vector<uint64_t> hits;
+  uint64_t hit_n = 0;
+  bool hits_lost = false;
 };
 
 struct Job {
@@ -59,6 +65,11 @@ struct Job {
   bool answered = false;            // pool_relax decided the job from its reserve
   uint64_t relaxes = 0;             // lowerings of the threshold that took effect (pool_relax)
   uint64_t candidates = 0;          // reserve records read from the GPUs and validated
+  // A sweep job (npow_submit_sweep): a bounded job (max_per_dev != 0: its devices' largest part) that never wins --
+  // its entries collect every hit of [start, start + count) (PoolEntry::bounded kEntryCollect, JobDev::hits), each
+  // device a contiguous part.  Only pool_wait_sweep collects its ticket; a part is never handed to another device.
+  bool sweep = false;
+  uint64_t count = 0;
   uint64_t start = 0, max_per_dev = 0, spacing = 0;
   const volatile uint32_t* cancel = nullptr;
   uint32_t weight = 1;    // 1, 2, 4 or 8 (npow_submit_weighted): its share of each GPU's workgroups among the live

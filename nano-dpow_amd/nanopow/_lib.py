@@ -39,6 +39,8 @@ NPOW_PATH_SEARCH = 0   # the stream the search and sweep kernels execute (four 5
 NPOW_PATH_SEQ = 1      # a second generated stream, scheduled without barriers
 NPOW_PATH_GENERIC = 2  # plain HIP C++ of the 12 rounds, one (root, nonce) per lane
 
+NPOW_SWEEP_JOB_HITS = 1 << 20  # hits one device keeps for one sweep job (Engine.submit_sweep)
+
 M64 = (1 << 64) - 1
 
 # Every symbol include/nanopow.h declares (tests/test_abi.py checks the export table).
@@ -50,7 +52,7 @@ EXPORTED_SYMBOLS = (
     "npow_set_pool_tuning", "npow_values_path", "npow_wait_info", "npow_device_stats_get_sized",
     "npow_abi_version", "npow_config_cpu_threads", "npow_wait_result", "npow_submit_weighted",
     "npow_promote", "npow_retarget", "npow_submit_background", "npow_ticket_background",
-    "npow_submit_reserve", "npow_ticket_reserve", "npow_relax",
+    "npow_submit_reserve", "npow_ticket_reserve", "npow_relax", "npow_submit_sweep", "npow_wait_sweep",
 )
 
 
@@ -145,6 +147,7 @@ class SweepResult:
     status: int            # NPOW_OK, or NPOW_CANCELLED (hits then holds what was found before it)
     hits: List[int]        # ascending (nonce - start); at most cap of them
     total: int             # exact number of hits (may exceed len(hits) only with status != OK)
+    nonces_done: Optional[int] = None  # a sweep job's (SweepTicket.wait): nonces hashed, == count when status is OK
 
 
 @dataclass
@@ -249,6 +252,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.npow_ticket_reserve.restype = ctypes.c_int
             lib.npow_relax.argtypes = [u64, u64, ctypes.POINTER(ctypes.c_uint32)]
             lib.npow_relax.restype = ctypes.c_int
+        if hasattr(lib, "npow_submit_sweep"):  # added within ABI 7: probed for
+            lib.npow_submit_sweep.argtypes = [u8p, u64, u64, u64, u64, p, pu64]
+            lib.npow_submit_sweep.restype = ctypes.c_int
+            lib.npow_wait_sweep.argtypes = [u64, ctypes.c_int64, p, u64, pu64, pu64]
+            lib.npow_wait_sweep.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -454,6 +462,55 @@ class Ticket:
             pass
 
 
+class SweepTicket:
+    """A submitted sweep job (npow_submit_sweep); wait() returns its SweepResult once."""
+
+    def __init__(self, engine: "Engine", ticket: int, cancel: Optional[CancelToken], cap: int) -> None:
+        self.engine = engine
+        self.ticket = ticket
+        self.cancel_token = cancel  # keeps the cancel word alive while the engine may read it
+        self.cap = cap
+        self.result: Optional[SweepResult] = None
+
+    def wait(self, timeout: Optional[float] = None) -> Optional[SweepResult]:
+        """Block until the job ends (timeout None) or up to `timeout` seconds; None if it is still running then.
+        The result's status is NPOW_OK (hits is the exact hit set of the range, nonces_done == count),
+        NPOW_CANCELLED (the hits found so far) or NPOW_ERR_CAPACITY (more hits than `cap`, or than
+        NPOW_SWEEP_JOB_HITS on one device: total is exact, hits holds the first ones); any other error raises."""
+        if self.result is not None:
+            return self.result
+        lib = self.engine.lib
+        out = (ctypes.c_uint64 * max(self.cap, 1))()
+        n, done = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        us = -1 if timeout is None else max(0, int(timeout * 1e6))
+        rc = lib.npow_wait_sweep(self.ticket, us, ctypes.addressof(out), self.cap, ctypes.byref(n), ctypes.byref(done))
+        if rc == NPOW_PENDING:
+            return None
+        self.cancel_token = None
+        self.ticket = 0  # collected, whatever the status
+        _check(rc, lib, ok=(NPOW_OK, NPOW_CANCELLED, NPOW_ERR_CAPACITY))
+        self.result = SweepResult(rc, list(out[: min(n.value, self.cap)]), n.value, done.value)
+        return self.result
+
+    def cancel(self) -> None:
+        if self.result is None and self.ticket:
+            _check(self.engine.lib.npow_cancel(self.ticket), self.engine.lib)
+
+    def __del__(self) -> None:
+        # An abandoned ticket: as Ticket.__del__ -- cancel the job and collect it, so the engine forgets it and
+        # stops reading the cancel word before that word is freed.
+        if self.result is not None or not getattr(self, "ticket", 0):
+            return
+        try:
+            lib = self.engine.lib
+            lib.npow_cancel(self.ticket)
+            n = ctypes.c_uint64(0)
+            if lib.npow_wait_sweep(self.ticket, 10_000_000, None, 0, ctypes.byref(n), None) == NPOW_PENDING:
+                _ORPHANED_CANCEL_WORDS.append(self.cancel_token)
+        except Exception:  # interpreter shutdown: the library may already be gone
+            pass
+
+
 class Engine:
     """Thin object wrapper over the C ABI (one per process is enough)."""
 
@@ -593,6 +650,19 @@ class Engine:
                                  ctypes.byref(n))
         _check(rc, self.lib, ok=(NPOW_OK, NPOW_CANCELLED))
         return SweepResult(rc, list(out[: min(n.value, cap)]), n.value)
+
+    def submit_sweep(self, root: bytes, threshold: int, start: int, count: int, device_mask: int = 0,
+                     cancel: Optional[CancelToken] = None, cap: int = 1 << 16) -> SweepTicket:
+        """Queue a sweep job and return at once (npow_submit_sweep): every hit of [start, start + count) enumerated
+        inside the work pool's launches, beside the live searches, where sweep() takes the devices from the pool.
+        SweepTicket.wait collects up to `cap` hits.  Keep `cancel` alive until then (the ticket holds a reference).
+        NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the loaded library has no npow_submit_sweep."""
+        if not hasattr(self.lib, "npow_submit_sweep"):
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_submit_sweep")
+        t = ctypes.c_uint64(0)
+        _check(self.lib.npow_submit_sweep(_root(root), threshold & M64, start & M64, count, device_mask,
+                                          cancel.address if cancel else None, ctypes.byref(t)), self.lib)
+        return SweepTicket(self, t.value, cancel, cap)
 
     def sweep(self, root: bytes, threshold: int, start: int, count: int, device_mask: int = 0,
               cap: int = 1 << 16, cancel: Optional[CancelToken] = None) -> List[int]:

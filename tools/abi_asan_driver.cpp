@@ -8,6 +8,7 @@
 // CPU with npow_work_value (the library's own CPU path; the hashlib oracle pins that
 // one in tests/test_oracle.py).  Exit status 0 = every check passed and ASan saw no
 // error.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdint>
@@ -132,6 +133,20 @@ static void sweeps(int tid, int n) {
     if (rc == NPOW_ERR_CAPACITY) g_capacity++;
     for (uint64_t k = 0; k < n_out && k < cap && k < ref.size(); k++)
       CHECK(out[k] == ref[k], "sweep hit %llu", (unsigned long long)k);
+
+    // the same range as a sweep job of the pool, beside the other threads' searches
+    uint64_t ticket = 0, n_job = 0, hashed = 0;
+    rc = npow_submit_sweep(root, thr, start, count, 1, nullptr, &ticket);
+    CHECK(rc == NPOW_OK, "submit_sweep rc %d", rc);
+    if (rc == NPOW_OK) {
+      std::fill(out.begin(), out.end(), 0);
+      rc = npow_wait_sweep(ticket, -1, out.data(), cap, &n_job, &hashed);
+      CHECK(rc == (ref.size() > cap ? NPOW_ERR_CAPACITY : NPOW_OK), "wait_sweep rc %d", rc);
+      CHECK(n_job == ref.size() && hashed == count, "sweep job count %llu hashed %llu", (unsigned long long)n_job,
+            (unsigned long long)hashed);
+      for (uint64_t k = 0; k < n_job && k < cap && k < ref.size(); k++)
+        CHECK(out[k] == ref[k], "sweep job hit %llu", (unsigned long long)k);
+    }
 
     uint64_t nonce = 0, value = 0, done = 0;
     rc = npow_search(root, ~uint64_t(0), start, g_bounded_mask, 4096 + i, nullptr, &nonce, &value, &done);
