@@ -427,6 +427,46 @@ int npow_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start
 int npow_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t cap, uint64_t* n_out,
                     uint64_t* nonces_done);
 
+/* Background sweep jobs (added within ABI 7; probe for the symbols): a sweep job that each GPU hashes only while no
+ * foreground job wants that GPU -- the class npow_submit_background gives a search, for the enumeration.  Same
+ * arguments and same split of the range as npow_submit_sweep; npow_wait_sweep collects the ticket with the same
+ * statuses and guarantees (NPOW_OK: every nonce hashed exactly once, hits strictly ascending by nonce - start, *n_out
+ * exact past the capacity, a duplicate is NPOW_ERR_INTERNAL, a dropped device fails the job); npow_cancel works on
+ * it; every other ticket call refuses it as it refuses any sweep ticket, npow_promote included (a background sweep job
+ * cannot be lifted to a foreground one).  count == 0 completes at once.
+ *
+ * On each device the job's part is hashed only in launches built while no foreground job is live on that device or
+ * waiting for it: searches from every other submit call, bounded searches and plain sweep jobs are foreground;
+ * background searches are not, and share a launch with the job as they do with a bounded search.  While held out the
+ * job keeps its slot, its generation and its place in the range.  A launch that holds it takes its span in chunks of
+ * 8,192 nonces per workgroup and ends within one chunk (~0.3 ms) once a foreground job arrives or the launch's time
+ * budget (npow_set_pool_tuning) passes; what it did not reach goes back to the job.  It is admitted as background
+ * searches are: behind every waiting foreground job, under the same cap on slots.
+ * CONTINUOUS FOREGROUND LOAD STARVES IT: the job makes no progress while any foreground job is live on its devices,
+ * for as long as that lasts.  That is the meaning of the class. */
+int npow_submit_sweep_background(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count,
+                                 uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket);
+
+/* A look at an uncollected sweep ticket, plain or background (npow_ticket_sweep). */
+typedef struct npow_sweep_info {
+  uint32_t size;          /* set by the caller; the library writes at most that many bytes */
+  uint32_t background;    /* 1: npow_submit_sweep_background */
+  uint64_t count;         /* nonces of the job's range */
+  uint64_t nonces_done;   /* nonces credited by the launches retired so far (the final count once finished) */
+  uint64_t hits;          /* hits read from the launches retired so far */
+  uint64_t launches;      /* launches that held an entry of the job, summed over its devices */
+  uint64_t launches_cut;  /* of those, launches that ended with part of their span unhashed: a yield or the time
+                           * budget (background jobs only; the part went back to the job) */
+  uint64_t held_us;       /* time the job sat admitted but left out of its devices' tables, summed over its devices */
+  uint32_t finished;      /* 1: npow_wait_sweep would return at once */
+  uint32_t pad;
+} npow_sweep_info;
+
+/* Progress of an uncollected sweep job's ticket (added within ABI 7; probe for the symbol).  Written up to out->size.
+ * NPOW_ERR_BAD_ARGUMENT for a search's ticket, an unknown or collected one, or out / out->size missing.  Never waits
+ * for a GPU. */
+int npow_ticket_sweep(uint64_t ticket, npow_sweep_info* out);
+
 /* Work values of `count` consecutive nonces start, start+1, ... for one root,
  * computed by the instruction stream the search and sweep kernels execute
  * (npow_values_kernel_ls2: the same uniform loads, priority runs and

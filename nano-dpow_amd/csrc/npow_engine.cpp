@@ -806,6 +806,26 @@ int npow_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start
   return pool_submit_sweep(root, threshold, start, count, device_mask, cancel, ticket);
 } catch (...) { return guard_exception(); }
 
+int npow_submit_sweep_background(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count,
+                                 uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket) try {
+  if (int rc = check_init()) return rc;
+  if (!root || !ticket) return fail(NPOW_ERR_BAD_ARGUMENT, "root and ticket are required");
+  return pool_submit_sweep(root, threshold, start, count, device_mask, cancel, ticket, true);
+} catch (...) { return guard_exception(); }
+
+int npow_ticket_sweep(uint64_t ticket, npow_sweep_info* out) try {
+  if (int rc = check_init()) return rc;
+  if (!out || out->size < offsetof(npow_sweep_info, count))
+    return fail(NPOW_ERR_BAD_ARGUMENT, "out with out->size set is required");
+  npow_sweep_info full{};
+  const int rc = pool_ticket_sweep(ticket, &full);
+  if (rc != NPOW_OK) return rc;
+  const uint32_t n = std::min<uint32_t>(out->size, (uint32_t)sizeof(full));
+  full.size = n;
+  memcpy(out, &full, n);
+  return NPOW_OK;
+} catch (...) { return guard_exception(); }
+
 int npow_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t cap, uint64_t* n_out,
                     uint64_t* nonces_done) try {
   if (int rc = check_init()) return rc;

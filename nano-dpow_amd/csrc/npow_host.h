@@ -220,7 +220,9 @@ int pool_ticket_reserve(uint64_t ticket, npow_reserve_info* out);  // npow_ticke
 int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered);  // npow_relax (answered: not null)
 // sweep jobs (npow_submit_sweep, npow_wait_sweep; arguments checked by the caller)
 int pool_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count, uint64_t device_mask,
-                      const volatile uint32_t* cancel, uint64_t* ticket);
+                      const volatile uint32_t* cancel, uint64_t* ticket,
+                      bool background = false);  // npow_submit_sweep_background
+int pool_ticket_sweep(uint64_t ticket, npow_sweep_info* out);  // npow_ticket_sweep (out: a full struct)
 int pool_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t cap, uint64_t* n_out,
                     uint64_t* nonces_done);
 static_assert(NPOW_SWEEP_JOB_HITS == kSweepHits, "the published capacity is the device's record set");

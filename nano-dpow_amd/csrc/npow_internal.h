@@ -6,6 +6,7 @@
 
 #include "npow_blake2b.h"
 #include "npow_weights.h"
+#include "npow_claims.h"
 #include "npow_hash_asm.inc"
 #include "npow_hash_asm_lockstep_ld.inc"
 
@@ -103,7 +104,11 @@ constexpr int kPoolDoneShards = 32;
 //  * bounded (max_nonces set; must cover its range exactly once): only the entry's own
 //    workgroups (g % n == e, rank r = g / n, k_e of them) run it, index = (it * 8 k_e + 8 r +
 //    wave) * 64 + lane (8 = kLsWaves), dense over [0, count) with count <= 8 k_e * iters * 64; others never
-//    enter it.
+//    enter it;
+//  * claimed (kEntryClaim, a background sweep job's: bounded and collecting too): the same workgroups, but each takes
+//    chunks of kClaimRows rows from the launch's claim counter of the slot -- chunk c, row r of it, index =
+//    ((c * kClaimRows + r) * 8 + wave) * 64 + lane (npow_claims.h) -- and the launch covers the first `claims` chunks
+//    of [0, count): all of them unless its time budget or a yield stopped the claims.
 struct PoolEntry {
   uint64_t u[NPOW_ASM_N_UNIFORMS];  // nonce-independent intermediates of the root
   uint64_t threshold;
@@ -114,7 +119,11 @@ struct PoolEntry {
   uint32_t bounded;  // bit 0 (kEntryBounded): dense mapping over the entry's own workgroups, no migrants.  Bit 1
                      // (kEntryCollect, with bit 0): a sweep job's entry (npow_submit_sweep) -- it never wins, every
                      // lane at or above the threshold is appended to the launch's hit records (PoolHits); bits 8..15:
-                     // the entry's region of the records, bits 16..20: the regions' size as a shift (pool_collect_*)
+                     // the entry's region of the records, bits 16..20: the regions' size as a shift (pool_collect_*).
+                     // Bit 2 (kEntryClaim, with bits 0 and 1): a background sweep job's entry
+                     // (npow_submit_sweep_background) -- its workgroups claim chunks of the span from the launch's
+                     // claim counter (PoolHits::claim, npow_claims.h) instead of walking the dense mapping, and stop
+                     // claiming at the launch's time budget or a yield
   uint32_t wsh;      // unbounded: 3 - log2(weight), weight in {1, 2, 4, 8} (npow_submit_weighted): wherever two
                      // entries' workgroup counts are compared, each is shifted left by its wsh first, so a job's
                      // share of the launch's workgroups is weight / (sum of weights).  Equal values compare as the
@@ -139,7 +148,8 @@ struct PoolTable {
   uint32_t iters;      // wave iterations of this launch (the cap; bounded entries' dense span)
   uint32_t budget;     // > 0: a wave on an unbounded entry stops once this many 100-MHz
                        // s_memrealtime ticks have passed since it started (all waves stop
-                       // together); 0 = iteration count only
+                       // together), and a workgroup on a claimed entry (kEntryClaim) claims no further
+                       // chunk; 0 = iteration count only
   uint64_t yield_base;    // PoolMailbox::ctl when the table was built: a polling wave that reads
                           // a different high half ends the launch's unbounded entries
   uint32_t ring;          // PoolMailbox::clk[ring]: this launch's clock records ...
@@ -225,7 +235,7 @@ constexpr int kPoolRing = 4;  // launch ring of the pool kernels (host: kEventRi
 // entry's region and the shift): a hit lane of slot s stores its nonce at rank n[s]++ of its entry's region, or not
 // at all past the region's end -- the counter keeps counting, so the hit count stays exact.
 constexpr uint32_t kSweepHits = 1u << 20;  // records per set (NPOW_SWEEP_JOB_HITS, include/nanopow.h)
-constexpr uint32_t kEntryBounded = 1u, kEntryCollect = 2u;
+constexpr uint32_t kEntryBounded = 1u, kEntryCollect = 2u, kEntryClaim = 4u;
 __host__ __device__ inline uint32_t pool_collect_flags(uint32_t region, uint32_t shift) {
   return kEntryBounded | kEntryCollect | (region << 8) | (shift << 16);
 }
@@ -233,6 +243,8 @@ __host__ __device__ inline uint32_t pool_collect_region(uint32_t bounded) { retu
 __host__ __device__ inline uint32_t pool_collect_shift(uint32_t bounded) { return (bounded >> 16) & 0x1fu; }
 struct PoolHits {
   unsigned long long n[kMaxSlots];  // hits of the slot's entry in this launch (may exceed its region)
+  unsigned long long claim[kMaxSlots];  // chunks claimed of the slot's claimed entry in this launch (kEntryClaim;
+                                        // zeroed and read with n; runs past the span's chunks, npow_claims.h)
   uint64_t rec[kSweepHits];         // the nonces, region by region, each in the order its waves came
 };
 struct PoolDevState {

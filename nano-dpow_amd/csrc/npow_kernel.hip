@@ -1003,6 +1003,27 @@ __device__ __forceinline__ void ls2_collect(const PoolTable* tab, PoolDevState* 
   if (hit && rank < room) ph->rec[(size_t)region * room + (size_t)rank] = nonce;
 }
 
+// A claimed collecting entry (kEntryClaim: a background sweep job, npow_submit_sweep_background; pool_body_ls2, BOUNDED
+// only).  Lane 0 of wave 0, before each chunk: the next chunk index of the entry's span from the launch's claim counter
+// of the slot (PoolHits::claim, zeroed in stream order with the hit counters: a count belongs to one launch of one
+// generation), or kNoEntry when the workgroup must claim no more -- a stop request is filed (the entry is dead or was
+// killed: the per-iteration path), the entry is dead, the launch's time budget has passed, the host has raised a yield
+// since the table was built (the pinned word, read past the caches: one read per chunk and workgroup), or the span is
+// used up.  A chunk once claimed is hashed to its end, so the launch covers exactly the first `claims` chunks of the
+// span (npow_claims.h: the host credits that prefix and hands the rest back).  One device-scope atomic per chunk.
+__device__ __forceinline__ uint32_t ls2_claim(const PoolTable* tab, PoolDevState* st, PoolMailbox* mb,
+                                              const PoolEntry* pe, uint32_t stop, uint64_t t_start) {
+  if (stop != ~0u) return kNoEntry;  // (the segment's stop word, read by the caller)
+  ConstEntry* ce = (ConstEntry*)(uintptr_t)pe;
+  const uint32_t slot = ce->slot;
+  if (slot >= (uint32_t)kMaxSlots) return kNoEntry;  // (never: the host's table; keeps the index in)
+  if (load_dead(st, slot) >= ce->gen) return kNoEntry;
+  if (tab->budget && (uint32_t)__builtin_amdgcn_s_memrealtime() - (uint32_t)t_start >= tab->budget) return kNoEntry;
+  if ((ls2_ctl(mb) >> 32) != (tab->yield_base >> 32)) return kNoEntry;
+  const unsigned long long k = atomicAdd(&st->hits[tab->ring & 1u].claim[slot], 1ull);
+  return k < (unsigned long long)claim_chunks(ce->count) ? (uint32_t)k : kNoEntry;
+}
+
 // Odd, so that it0 -> -it0 * kPollStride is a bijection modulo every power of two; its residues mod 2^10..2^13 step
 // by 0.43, 0.22, 0.11 and 0.80 of the range (the fractional part of the golden ratio in 32 bits).
 constexpr uint32_t kPollStride = 0x9E3779B9u;
@@ -1076,8 +1097,35 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
     unsigned long long* const dead_p = &st->slot[c.slot].dead;
     uint32_t b = it * c.K + c.j;
     uint64_t nonce = c.base + ((uint64_t)b << 6) + lane;
-    const uint64_t step = (uint64_t)c.K << 6;
+    uint64_t step = (uint64_t)c.K << 6;
     uint32_t done = 0;
+    for (;;) {  // (a claimed entry: once per chunk; every other entry: once)
+    if constexpr (BOUNDED) {
+      // Background sweep jobs (kEntryClaim): the entry's own workgroups do not walk the dense mapping; each takes
+      // chunks of kClaimRows rows of the span from the launch's claim counter (ls2_claim) until the span is used up
+      // or the launch must end.  Wave 0 claims and broadcasts the index through LDS (two barriers: every wave has
+      // read it before the next claim writes it, as npow_sweep_kernel_ls2's row claims).  Within a chunk `it` is the
+      // row: block it * 8 + wave, the loop below unchanged -- its lane mask (last_b, tail), ls2_collect, the dead
+      // word and the stop requests -- and a request filed in a chunk is seen by the next claim.
+      if (c.bounded & kEntryClaim) {
+        __shared__ uint32_t s_claim;
+        if (wv == 0 && lane == 0)
+          s_claim = ls2_claim(tab, st, mb, pe,
+                              __hip_atomic_load(&s_stop[sw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), t_start);
+        __syncthreads();
+        const uint32_t ci = __builtin_amdgcn_readfirstlane(
+            __hip_atomic_load(&s_claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        __syncthreads();
+        if (ci == kNoEntry) break;
+        c.K = kLsWaves;
+        c.j = wv;
+        step = (uint64_t)kLsWaves << 6;
+        it = claim_row_first(ci);
+        c.it_end = claim_row_end(c.last_b / kLsWaves + 1u, ci);
+        b = it * kLsWaves + wv;
+        nonce = c.base + ((uint64_t)b << 6) + lane;
+      }
+    }
     while (it < c.it_end) {
       const uint32_t verdict = __hip_atomic_load(&s_stop[sw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       const uint64_t dead = __hip_atomic_load(dead_p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1217,6 +1265,11 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
       nonce += step;
       b += c.K;
       __builtin_amdgcn_s_barrier();
+    }
+    if constexpr (BOUNDED) {
+      if (c.bounded & kEntryClaim) continue;  // the next chunk, or none (ls2_claim: a stop request among the reasons)
+    }
+    break;
     }
     // the workgroup's count, added by wave 0 before it leaves the entry (early finish, ls2_leave):
     // one atomic and no fence per wave

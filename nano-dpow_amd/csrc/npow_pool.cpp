@@ -28,6 +28,11 @@
 // the launch's hit records (PoolHits), which the worker reads as each launch retires (collect_hits); pool_wait_sweep
 // merges them.  DESIGN.md section 1 "Sweep jobs".
 //
+// A background sweep job (npow_submit_sweep_background; Job::sweep with Job::background) is a sweep job this file
+// leaves out of a device's tables while a foreground job is live there (hold_out).  Its entries are claimed ones
+// (kEntryClaim): a launch covers a prefix of its span, told by its claim counter, and ends at the time budget or a
+// yield; collect_hits credits the prefix and hands the rest back.  DESIGN.md section 1 "Background sweep jobs".
+//
 // Threads: one persistent worker per device (started by npow_init) owns the device's
 // stream, its slot table and up to two launches in flight (the second is queued only near
 // the end of the first one's budget, or at once behind a launch with no live entry left);
@@ -359,6 +364,10 @@ struct Adoption {
   bool readback = false;   // done-shard read-back queued (ev_done[slot] marks it)
   bool no_readback = false;  // finished early and not sampled for verification: freed once inflight is empty
   bool fresh = false;      // adopted since the last launch was built
+  bool held = false;       // a background sweep job's slot left out of the tables: a foreground job wants the device
+                           // (hold_out); it keeps its generation and its place in the range
+  uint64_t claimed = 0;    // a background sweep job: the nonces its retired launches' claims covered in this generation
+                           // (collect_hits), checked against the slot's done counts when it retires
   bool new_job = false;    // adopted for the first time on this device (not a re-adoption)
   bool fin_seen = false;   // the kernel published this generation's final count (PoolMailbox::fin) ...
   bool early = false;      // ... and the job was finished from it before retiring
@@ -392,12 +401,21 @@ struct PoolInflight {
   bool bounded;         // its table holds a bounded entry: no entry of the launch carries the background flag
   // Its collecting entries (sweep jobs): the slot and generation of each, and its region of the launch's hit records
   // (PoolHits; the set is ring & 1), `room` records from record region * room on.  Read when the launch retires.
+  // A claimed entry (a background sweep job's, kEntryClaim) also has its span: the launch's claim counter of the slot
+  // tells which prefix of it was covered (npow_claims.h).
   struct Collect {
     int slot;
     uint64_t gen;
     uint32_t region, room;
+    bool claim;
+    uint64_t base, count;
   };
   std::vector<Collect> collect;
+  bool claimed() const {  // it holds a claimed entry: a foreground search does not join it, a yield ends it
+    for (const Collect& c : collect)
+      if (c.claim) return true;
+    return false;
+  }
 };
 
 // The most nonces a collecting entry of threshold `threshold` takes in one launch, so that its hits fit the `room`
@@ -479,7 +497,7 @@ class Worker {
   }
   bool live_slot(int except = -1) const {  // a slot (other than `except`) some launch in flight is hashing
     for (int s = 0; s < kMaxSlots; ++s)
-      if (s != except && slots_[s].state == SlotState::kActive && !slots_[s].fresh) return true;
+      if (s != except && slots_[s].state == SlotState::kActive && !slots_[s].fresh && !slots_[s].held) return true;
     return false;
   }
   bool foreground_live(int except) const {  // live_slot, of a foreground job (caller holds g_pool.mu: Job::background)
@@ -542,6 +560,7 @@ class Worker {
   }
   void check_slots();
   void build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded);
+  uint32_t hold_out(int* idx, uint32_t n);
   int launch(bool empty_linger = false);
   int queue_readbacks();
   int collect_hits(const PoolInflight& f);
@@ -658,6 +677,9 @@ bool Worker::dyn_add(int s) {
   const PoolShape sh = pool_shape(d_);
   const PoolInflight& f = q_.back();
   if (!f.counted) return false;  // a one-entry launch: the new job ends it (a yield) instead
+  // a launch of background sweep jobs: its workgroups stay on their claimed entries until the spans are used up, so a
+  // foreground job that joined would wait for that; it ends the launch instead (a yield: within one chunk)
+  if (f.claimed() && !j.background) return false;
   if ((uint32_t)((uint32_t)ctl_ - (uint32_t)f.dyn_base) >= (uint32_t)kDynEntries) return false;
   if ((ctl_ >> 32) != (f.yield_base >> 32)) return false;  // it is ending
   if (q_.size() == 2) {
@@ -701,10 +723,22 @@ void Worker::yield_if_long() {
   int live = 0;
   for (const Slot& sl : slots_)
     if (sl.state == SlotState::kActive && !sl.fresh && !sl.job->max_per_dev) ++live;
-  if (live >= kYieldMaxLive) return;
+  // (a launch of background sweep jobs is ended whatever it holds: nothing foreground is in it -- hold_out -- and the
+  // job that waits cannot join it)
+  bool claimed = false;
+  for (const PoolInflight& f : q_) claimed = claimed || f.claimed();
+  if (live >= kYieldMaxLive && !claimed) return;
   bool any = false;
   for (int s = 0; s < kMaxSlots; ++s) {
     Slot& sl = slots_[s];
+    // a background sweep job in the running launch: the yield ends its claims; the slot stays as it is, and what the
+    // launch did not reach goes back to the job when the launch retires (collect_hits)
+    // (held from now on, as hold_out holds it: the next table is queued behind the ending launch at once -- live_slot)
+    if (sl.state == SlotState::kActive && !sl.inflight.empty() && sl.job->claimed()) {
+      any = true;
+      if (!sl.held) sl.job->dev[sl.k].held_since = now_us();
+      sl.held = true;
+    }
     if (sl.state != SlotState::kActive || sl.fresh || sl.job->max_per_dev) continue;
     sl.requeue = true;
     stop_slot(s, false);
@@ -930,7 +964,15 @@ void Worker::check_slots() {
       }
       stop_slot(s, true);  // in-flight waves stop
       sl.stop_us = now_us();
-    } else if (sl.no_more) {
+    } else if (sl.no_more && !(j.claimed() && !sl.inflight.empty())) {
+      // (a background sweep job's launches may hand part of their spans back: its slot stays until they have retired)
+      if (sl.held) {  // (held at a yield, and the launches covered all that was left)
+        std::lock_guard<std::mutex> g(g_pool.mu);
+        JobDev& jd = j.dev[sl.k];
+        jd.held_us += now_us() - jd.held_since;
+        jd.held_since = 0;
+        sl.held = false;
+      }
       stop_slot(s, false);
     }
   }
@@ -1001,12 +1043,12 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
         // the span a bounded job takes, unless the threshold is so low that its hits would not fit the region
         const uint32_t room = kSweepHits >> cshift, region = (uint32_t)collect_.size();
         take_entry(sl, t.e[e], std::min(sh.own(e, n, iters), collect_span(j.threshold, room)), seq_, t_issue);
-        t.e[e].bounded = pool_collect_flags(region, cshift);
+        t.e[e].bounded = pool_collect_flags(region, cshift) | (j.claimed() ? kEntryClaim : 0u);
         t.e[e].wsh = pool_wsh(j.weight);
         weights[e] = j.weight;
         bgs[e] = 0;
         *bounded = true;
-        collect_.push_back({idx[e], sl.gen, region, room});
+        collect_.push_back({idx[e], sl.gen, region, room, j.claimed(), t.e[e].base, t.e[e].count});
         continue;
       }
       // the next part of the device's queue of ranges: a bounded job's own waves cover it
@@ -1049,6 +1091,38 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
   }
 }
 
+// Background sweep jobs among the slots idx[] of the next table: while a foreground job is live on this device -- in a
+// launch in flight, or among idx[] itself, waiting for this table -- their slots are left out of it (and of live_slot():
+// nothing waits for them).  They keep their generation and their queue of ranges; the time they sit out is the job's
+// held_us (npow_ticket_sweep).  Returns the new n.
+uint32_t Worker::hold_out(int* idx, uint32_t n) {
+  std::lock_guard<std::mutex> g(g_pool.mu);  // Job::background of the searches (pool_promote), JobDev
+  bool fg = foreground_live(-1);
+  for (uint32_t e = 0; e < n && !fg; ++e) fg = !slots_[idx[e]].job->background;
+  const double t = now_us();
+  uint32_t m = 0;
+  for (uint32_t e = 0; e < n; ++e) {
+    Slot& sl = slots_[idx[e]];
+    if (!sl.job->claimed()) {
+      idx[m++] = idx[e];
+      continue;
+    }
+    JobDev& jd = sl.job->dev[sl.k];
+    if (fg) {
+      if (!sl.held) jd.held_since = t;
+      sl.held = true;
+      continue;
+    }
+    if (sl.held) {
+      jd.held_us += t - jd.held_since;
+      jd.held_since = 0;
+      sl.held = false;
+    }
+    idx[m++] = idx[e];
+  }
+  return m;
+}
+
 int Worker::launch(bool empty_linger) {
   if (q_.size() >= 2 || d_.dead) return NPOW_OK;
   // The second launch in flight only has to be queued before the running one ends (its budget
@@ -1059,8 +1133,13 @@ int Worker::launch(bool empty_linger) {
   if (q_.size() == 1 && g_budget_us.load() > 0 && budget_left_us() > kPrelaunchUs && live_slot()) return NPOW_OK;
   uint32_t n = 0;
   int idx[kMaxSlots];
+  bool claimed = false;  // (Job::sweep and a sweep job's class never change: read without the pool lock)
   for (int s = 0; s < kMaxSlots; ++s)
-    if (slots_[s].state == SlotState::kActive && !slots_[s].no_more) idx[n++] = s;
+    if (slots_[s].state == SlotState::kActive && !slots_[s].no_more) {
+      idx[n++] = s;
+      claimed = claimed || slots_[s].job->claimed();
+    }
+  if (claimed) n = hold_out(idx, n);
   if (n == 0 && !empty_linger) return NPOW_OK;
   if (!live_slot()) end_linger();  // (step() has raised it already when a job waits; a bounded range's next part)
   PoolTable& t = *d_.h_tab[ring_];
@@ -1082,7 +1161,7 @@ int Worker::launch(bool empty_linger) {
   // Sweep jobs: this launch's set of hit records (PoolHits) starts from zero counts, in stream order.  Its previous
   // user, the launch before the last, has retired -- at most two are in flight -- and its hits were read then.
   if (!collect_.empty())
-    HIPTRY(hipMemsetAsync(d_.pst->hits[r & 1].n, 0, sizeof(d_.pst->hits[r & 1].n), d_.stream));
+    HIPTRY(hipMemsetAsync(&d_.pst->hits[r & 1], 0, offsetof(PoolHits, rec), d_.stream));  // (n and claim)
   if (n <= (uint32_t)kArgEntries) {
     HIPTRY(hipEventRecord(d_.ev_start[r], d_.stream));
     HIPTRY(launch_pool_arg(d_.stream, sh.grid, t, bounded, d_.pst, d_.pmb_dev));
@@ -1172,7 +1251,9 @@ int Worker::collect_hits(const PoolInflight& f) {
   if (f.collect.empty()) return NPOW_OK;
   DEVCHECK(d_, "pool hit read-back");
   PoolHits* set = &d_.pst->hits[f.ring & 1];
-  HIPTRY(hipMemcpyAsync(d_.h_hit_n, set->n, sizeof(set->n), hipMemcpyDeviceToHost, d_.hit_stream));
+  static_assert(offsetof(PoolHits, claim) == sizeof(PoolHits::n) && offsetof(PoolHits, rec) == 2 * sizeof(PoolHits::n),
+                "the hit and claim counters are read with one copy");
+  HIPTRY(hipMemcpyAsync(d_.h_hit_n, set, offsetof(PoolHits, rec), hipMemcpyDeviceToHost, d_.hit_stream));
   HIPTRY(hipStreamSynchronize(d_.hit_stream));
   for (const PoolInflight::Collect& c : f.collect) {
     Slot& sl = slots_[c.slot];
@@ -1192,6 +1273,28 @@ int Worker::collect_hits(const PoolInflight& f) {
     if (n > stored) jd.hits_lost = true;
     const uint64_t take = std::min<uint64_t>(stored, (uint64_t)NPOW_SWEEP_JOB_HITS - jd.hits.size());
     jd.hits.insert(jd.hits.end(), d_.h_hits, d_.h_hits + take);
+    // What the launch covered of the entry's span: all of it -- or, a claimed entry, the first `claims` chunks
+    // (npow_claims.h); the rest goes back to the front of the device's queue of ranges (kept in range order: with
+    // two launches in flight the later one's span lies after this one's), and the slot is offered to the next table.
+    // Nothing is credited once the slot's generation has stopped (a cancel: its launches ended part-way; the done
+    // counts' read-back tells what was hashed).
+    jd.launches++;
+    if (sl.stop_us > 0 || sl.job->decided.load()) continue;
+    uint64_t covered = c.count;
+    if (c.claim) {
+      covered = claim_prefix(c.count, d_.h_hit_n[kMaxSlots + c.slot]);
+      sl.claimed += covered;
+      for (Slot::Issued& r : sl.inflight)
+        if (r.seq == f.seq && r.base == c.base) r.count = covered;
+      if (covered < c.count) {
+        jd.launches_cut++;
+        jd.todo.push_front({c.base + covered, c.count - covered});
+        std::sort(jd.todo.begin(), jd.todo.end(),
+                  [start](const Range& x, const Range& y) { return x.base - start < y.base - start; });
+        sl.no_more = false;
+      }
+    }
+    jd.progress += covered;
   }
   return NPOW_OK;
 }
@@ -1310,6 +1413,14 @@ int Worker::retire_slots() {
       std::lock_guard<std::mutex> g(g_pool.mu);
       Job& j = *sl.job;
       credit_job_locked(sl, c);
+      if (j.claimed() && !j.decided && !d_.dead && c.done != sl.claimed) {
+        // a background sweep job: the nonces its workgroups counted are not the prefixes its launches' claims covered
+        j.err = "background sweep job: device " + std::to_string(d_.id) + " hashed " + std::to_string(c.done) +
+                " nonces where its claims cover " + std::to_string(sl.claimed);
+        decide_locked(j, NPOW_ERR_INTERNAL);
+        g_pool.decisions.fetch_add(1, std::memory_order_release);
+        notify_workers_locked();
+      }
       if (d_.dead) {
         abandon_locked(sl.job, sl.k, d_.dead_code, d_.dead_msg);  // survivors take what is left
       } else if (!j.decided && (sl.requeue || !j.dev[sl.k].todo.empty())) {
@@ -1563,9 +1674,9 @@ int pool_device_init(Device& d) {
   // last 16 MiB of PoolDevState)
   HIPTRY(hipStreamCreateWithFlags(&d.hit_stream, hipStreamNonBlocking));
   void* hn = nullptr;
-  HIPTRY(hipHostMalloc(&hn, sizeof(PoolHits::n) + (size_t)kSweepHits * sizeof(uint64_t), hipHostMallocDefault));
-  d.h_hit_n = (unsigned long long*)hn;
-  d.h_hits = (uint64_t*)((char*)hn + sizeof(PoolHits::n));
+  HIPTRY(hipHostMalloc(&hn, offsetof(PoolHits, rec) + (size_t)kSweepHits * sizeof(uint64_t), hipHostMallocDefault));
+  d.h_hit_n = (unsigned long long*)hn;  // (the hit counters, then the claim counters)
+  d.h_hits = (uint64_t*)((char*)hn + offsetof(PoolHits, rec));
   return NPOW_OK;
 }
 
@@ -2041,9 +2152,10 @@ int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered) {
 // GPUs of the mask, as npow_sweep splits it (a GPU whose part would be empty is left out); each worker reads its
 // launches' hits as they retire (collect_hits), and pool_wait_sweep merges the devices' lists.
 int pool_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count, uint64_t device_mask,
-                      const volatile uint32_t* cancel, uint64_t* ticket) {
+                      const volatile uint32_t* cancel, uint64_t* ticket, bool background) {
   auto j = std::make_shared<Job>();
   j->sweep = true;
+  j->background = background;  // (npow_submit_sweep_background: admitted as a background search is, admit_locked)
   j->count = count;
   j->pre = host_precompute(root);
   npow_asm_uniforms(j->pre.m, j->u);
@@ -2086,6 +2198,31 @@ int pool_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start
     admit_locked();
   }
   *ticket = j->ticket;
+  return NPOW_OK;
+}
+
+int pool_ticket_sweep(uint64_t ticket, npow_sweep_info* out) {
+  std::lock_guard<std::mutex> g(g_pool.mu);
+  auto it = g_pool.tickets.find(ticket);
+  if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  const Job& j = *it->second;
+  if (!j.sweep) return fail(NPOW_ERR_BAD_ARGUMENT, "npow_ticket_sweep: the ticket is a search's");
+  const bool fin = j.finished.load();
+  const double t = fin ? j.t_finish : now_us();
+  out->background = j.background ? 1u : 0u;
+  out->count = j.count;
+  out->finished = fin ? 1u : 0u;
+  double held = 0;
+  uint64_t progress = 0;
+  for (const JobDev& jd : j.dev) {
+    progress += jd.progress;
+    out->hits += jd.hit_n;
+    out->launches += jd.launches;
+    out->launches_cut += jd.launches_cut;
+    held += jd.held_us + (jd.held_since > 0 && t > jd.held_since ? t - jd.held_since : 0.0);
+  }
+  out->nonces_done = fin ? j.done : std::max(j.done, progress);
+  out->held_us = (uint64_t)held;
   return NPOW_OK;
 }
 

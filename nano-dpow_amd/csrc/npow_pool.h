@@ -47,6 +47,13 @@ struct JobDev {
   std::vector<uint64_t> hits;
   uint64_t hit_n = 0;
   bool hits_lost = false;
+  // What npow_ticket_sweep reports of a sweep job on this device (Worker::collect_hits, Worker::hold_out).
+  // progress: the nonces the retired launches covered (a launch's whole span; of a background job's launch the prefix
+  // its claims covered, npow_claims.h).  launches_cut: launches of a background job that ended with part of their span
+  // unhashed (a yield, the time budget).  held_us / held_since: how long the job's slot was left out of this device's
+  // tables because a foreground job wanted the device, and since when it is (0 = it is not).
+  uint64_t progress = 0, launches = 0, launches_cut = 0;
+  double held_us = 0, held_since = 0;
 };
 
 struct Job {
@@ -68,7 +75,11 @@ struct Job {
   // A sweep job (npow_submit_sweep): a bounded job (max_per_dev != 0: its devices' largest part) that never wins --
   // its entries collect every hit of [start, start + count) (PoolEntry::bounded kEntryCollect, JobDev::hits), each
   // device a contiguous part.  Only pool_wait_sweep collects its ticket; a part is never handed to another device.
+  // With `background` set (npow_submit_sweep_background; it never changes: npow_promote refuses the ticket) its entries
+  // are claimed ones (kEntryClaim) and a device leaves its slot out of every table built while a foreground job is live
+  // there (Worker::hold_out).
   bool sweep = false;
+  bool claimed() const { return sweep && background; }
   uint64_t count = 0;
   uint64_t start = 0, max_per_dev = 0, spacing = 0;
   const volatile uint32_t* cancel = nullptr;

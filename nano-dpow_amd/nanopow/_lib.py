@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "npow_abi_version", "npow_config_cpu_threads", "npow_wait_result", "npow_submit_weighted",
     "npow_promote", "npow_retarget", "npow_submit_background", "npow_ticket_background",
     "npow_submit_reserve", "npow_ticket_reserve", "npow_relax", "npow_submit_sweep", "npow_wait_sweep",
+    "npow_submit_sweep_background", "npow_ticket_sweep",
 )
 
 
@@ -140,6 +141,35 @@ class ReserveInfo(ctypes.Structure):
         ("relaxes", ctypes.c_uint64),
         ("candidates", ctypes.c_uint64),
     ]
+
+
+class _SweepInfoStruct(ctypes.Structure):
+    """npow_sweep_info as the C ABI lays it out (npow_ticket_sweep)."""
+    _fields_ = [
+        ("size", ctypes.c_uint32),
+        ("background", ctypes.c_uint32),
+        ("count", ctypes.c_uint64),
+        ("nonces_done", ctypes.c_uint64),
+        ("hits", ctypes.c_uint64),
+        ("launches", ctypes.c_uint64),
+        ("launches_cut", ctypes.c_uint64),
+        ("held_us", ctypes.c_uint64),
+        ("finished", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32),
+    ]
+
+
+@dataclass
+class SweepInfo:
+    """A look at an uncollected sweep job (SweepTicket.info, npow_ticket_sweep)."""
+    background: bool       # submitted with background=True
+    count: int             # nonces of the range
+    nonces_done: int       # credited by the launches retired so far
+    hits: int              # read from the launches retired so far
+    launches: int          # launches that held an entry of the job, summed over its devices
+    launches_cut: int      # of those, launches a yield or the time budget ended before their span was hashed
+    held_us: int           # time the job sat admitted but left out of its devices' tables
+    finished: bool         # wait() would return at once
 
 
 @dataclass
@@ -257,6 +287,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.npow_submit_sweep.restype = ctypes.c_int
             lib.npow_wait_sweep.argtypes = [u64, ctypes.c_int64, p, u64, pu64, pu64]
             lib.npow_wait_sweep.restype = ctypes.c_int
+        if hasattr(lib, "npow_submit_sweep_background"):  # added within ABI 7: probed for
+            lib.npow_submit_sweep_background.argtypes = [u8p, u64, u64, u64, u64, p, pu64]
+            lib.npow_submit_sweep_background.restype = ctypes.c_int
+            lib.npow_ticket_sweep.argtypes = [u64, ctypes.POINTER(_SweepInfoStruct)]
+            lib.npow_ticket_sweep.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -492,6 +527,20 @@ class SweepTicket:
         self.result = SweepResult(rc, list(out[: min(n.value, self.cap)]), n.value, done.value)
         return self.result
 
+    def info(self) -> SweepInfo:
+        """The job's progress so far (npow_ticket_sweep); never waits for a GPU.  NanoPowError(NPOW_ERR_BAD_ARGUMENT)
+        once the ticket is collected, or when the loaded library has no npow_ticket_sweep."""
+        lib = self.engine.lib
+        if not hasattr(lib, "npow_ticket_sweep"):
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_ticket_sweep")
+        if not self.ticket:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the sweep ticket is collected")
+        i = _SweepInfoStruct()
+        i.size = ctypes.sizeof(_SweepInfoStruct)
+        _check(lib.npow_ticket_sweep(self.ticket, ctypes.byref(i)), lib)
+        return SweepInfo(bool(i.background), i.count, i.nonces_done, i.hits, i.launches, i.launches_cut, i.held_us,
+                         bool(i.finished))
+
     def cancel(self) -> None:
         if self.result is None and self.ticket:
             _check(self.engine.lib.npow_cancel(self.ticket), self.engine.lib)
@@ -652,16 +701,20 @@ class Engine:
         return SweepResult(rc, list(out[: min(n.value, cap)]), n.value)
 
     def submit_sweep(self, root: bytes, threshold: int, start: int, count: int, device_mask: int = 0,
-                     cancel: Optional[CancelToken] = None, cap: int = 1 << 16) -> SweepTicket:
+                     cancel: Optional[CancelToken] = None, cap: int = 1 << 16, *,
+                     background: bool = False) -> SweepTicket:
         """Queue a sweep job and return at once (npow_submit_sweep): every hit of [start, start + count) enumerated
         inside the work pool's launches, beside the live searches, where sweep() takes the devices from the pool.
         SweepTicket.wait collects up to `cap` hits.  Keep `cancel` alive until then (the ticket holds a reference).
-        NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the loaded library has no npow_submit_sweep."""
-        if not hasattr(self.lib, "npow_submit_sweep"):
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_submit_sweep")
+        background=True (npow_submit_sweep_background): each GPU hashes the job only while no foreground job wants
+        it, and a search that arrives waits one short chunk; continuous foreground load starves the job.
+        NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the loaded library lacks the call."""
+        name = "npow_submit_sweep_background" if background else "npow_submit_sweep"
+        if not hasattr(self.lib, name):
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, f"the loaded libnanopow has no {name}")
         t = ctypes.c_uint64(0)
-        _check(self.lib.npow_submit_sweep(_root(root), threshold & M64, start & M64, count, device_mask,
-                                          cancel.address if cancel else None, ctypes.byref(t)), self.lib)
+        _check(getattr(self.lib, name)(_root(root), threshold & M64, start & M64, count, device_mask,
+                                       cancel.address if cancel else None, ctypes.byref(t)), self.lib)
         return SweepTicket(self, t.value, cancel, cap)
 
     def sweep(self, root: bytes, threshold: int, start: int, count: int, device_mask: int = 0,

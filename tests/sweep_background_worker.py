@@ -1,0 +1,47 @@
+"""Child process of tests/test_gpu_sweep_background.py: one background sweep job split over two CU partitions.
+Run with NANOPOW_VIRTUAL_DEVICES=2 (two logical devices over the one physical GPU, each with its own stream, hit
+records, claim counters and worker): npow_submit_sweep_background of the first 2^24 fixture of
+tests/golden/sweeps_small.json over both devices with a 1-ms launch budget (each partition's half, 2^23 nonces, is
+about a budget's worth: whether a launch is cut is up to the box, and printed).  The merged hit set must equal the fixture's and the devices' nonce counters must add
+up to the range, each device holding its half.  Prints one JSON line; exits non-zero on any mismatch."""
+import json
+import os
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, os.path.join(ROOT, "nano-dpow_amd"))
+
+from nanopow import _lib  # noqa: E402
+
+
+def main():
+    eng = _lib.Engine()
+    G = eng.n_devices
+    assert G == int(os.environ["NANOPOW_VIRTUAL_DEVICES"]) == 2, G
+    with open(os.path.join(HERE, "golden", "sweeps_small.json")) as f:
+        c = json.load(f)["cases"][-3]
+    assert c["count"] == 1 << 24
+    for d in range(G):
+        eng.reset_stats(d)
+    eng.set_pool_tuning(budget_us=1000)
+    t = eng.submit_sweep(bytes.fromhex(c["root"]), int(c["threshold"], 16), int(c["start"], 16), c["count"],
+                         device_mask=0, background=True)
+    while not t.info().finished:
+        time.sleep(0.001)
+    i = t.info()
+    r = t.wait(60)
+    assert r is not None and r.status == _lib.NPOW_OK, r
+    assert [f"{h:016x}" for h in r.hits] == c["hits"], (len(r.hits), len(c["hits"]))
+    assert r.total == len(c["hits"]) and r.nonces_done == c["count"]
+    per = [eng.stats(d).nonces for d in range(G)]
+    assert per == [c["count"] // 2] * 2, per
+    print(json.dumps({"ok": True, "devices": G, "hits": len(r.hits), "nonces_done": r.nonces_done,
+                      "nonces_per_device": per, "launches": i.launches, "launches_cut": i.launches_cut,
+                      "affinity": [sum(eng.stats(d).affinity_checks for d in range(G)),
+                                   sum(eng.stats(d).affinity_failures for d in range(G))]}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -148,6 +148,35 @@ static void sweeps(int tid, int n) {
         CHECK(out[k] == ref[k], "sweep job hit %llu", (unsigned long long)k);
     }
 
+    // ... and as a background sweep job, held out while the other threads' searches are live and cut by their
+    // yields: the host's hold, prefix and remainder accounting, looked at with npow_ticket_sweep while it runs
+    ticket = 0, n_job = 0, hashed = 0;
+    rc = npow_submit_sweep_background(root, thr, start, count, 1, nullptr, &ticket);
+    CHECK(rc == NPOW_OK, "submit_sweep_background rc %d", rc);
+    if (rc == NPOW_OK) {
+      npow_sweep_info si{};
+      si.size = sizeof(si);
+      rc = npow_ticket_sweep(ticket, &si);
+      CHECK(rc == NPOW_OK && si.background == 1 && si.count == count && si.nonces_done <= count,
+            "ticket_sweep rc %d background %u done %llu", rc, si.background, (unsigned long long)si.nonces_done);
+      npow_sweep_info small{};
+      small.size = 16;  // a caller of an older struct: written up to its size
+      rc = npow_ticket_sweep(ticket, &small);
+      CHECK(rc == NPOW_OK && small.size == 16 && small.nonces_done == 0 && small.hits == 0, "ticket_sweep sized rc %d", rc);
+      std::fill(out.begin(), out.end(), 0);
+      while ((rc = npow_wait_sweep(ticket, 2000, out.data(), cap, &n_job, &hashed)) == NPOW_PENDING) {
+        si.size = sizeof(si);
+        CHECK(npow_ticket_sweep(ticket, &si) == NPOW_OK && si.launches_cut <= si.launches, "ticket_sweep while pending");
+      }
+      CHECK(rc == (ref.size() > cap ? NPOW_ERR_CAPACITY : NPOW_OK), "wait_sweep (background) rc %d", rc);
+      CHECK(n_job == ref.size() && hashed == count, "background sweep job count %llu hashed %llu",
+            (unsigned long long)n_job, (unsigned long long)hashed);
+      for (uint64_t k = 0; k < n_job && k < cap && k < ref.size(); k++)
+        CHECK(out[k] == ref[k], "background sweep job hit %llu", (unsigned long long)k);
+      si.size = sizeof(si);
+      CHECK(npow_ticket_sweep(ticket, &si) == NPOW_ERR_BAD_ARGUMENT, "ticket_sweep on a collected ticket");
+    }
+
     uint64_t nonce = 0, value = 0, done = 0;
     rc = npow_search(root, ~uint64_t(0), start, g_bounded_mask, 4096 + i, nullptr, &nonce, &value, &done);
     CHECK(rc == NPOW_EXHAUSTED || rc == NPOW_OK, "bounded rc %d", rc);
