@@ -76,7 +76,10 @@ extern "C" {
  * search that hashes only on workgroups no other search wants) and npow_ticket_background (its class now);
  * npow_submit_reserve (a search that keeps the best nonce it passes between a reserve threshold and its own),
  * npow_ticket_reserve (a look at that nonce) and npow_relax (lower the threshold of a running search, answered at once
- * from the reserve when it qualifies), with NPOW_RESERVE_MIN and npow_reserve_info. */
+ * from the reserve when it qualifies), with NPOW_RESERVE_MIN and npow_reserve_info; the sweep jobs
+ * (npow_submit_sweep, npow_wait_sweep, npow_submit_sweep_background, npow_ticket_sweep) and the best jobs
+ * (npow_submit_best, npow_wait_best, npow_ticket_best: the strongest nonce of a range), each described at its
+ * declaration. */
 #define NPOW_ABI_VERSION 7
 
 /* The lowest reserve threshold npow_submit_reserve takes.  A wave of a search with a reserve enters the kernel's rare
@@ -466,6 +469,56 @@ typedef struct npow_sweep_info {
  * NPOW_ERR_BAD_ARGUMENT for a search's ticket, an unknown or collected one, or out / out->size missing.  Never waits
  * for a GPU. */
 int npow_ticket_sweep(uint64_t ticket, npow_sweep_info* out);
+
+/* Best jobs (added within ABI 7; probe for the symbols): the nonce of [start, start + count) with the highest work
+ * value, as a job of the work pool -- "hash exactly count nonces for this root and give me the strongest".  A sweep
+ * job's sibling: hashed by the kernels that answer searches, in launches shared with up to 63 other jobs, but its
+ * waves compare with the best value seen so far instead of a fixed threshold and record only what beats it, so the
+ * answer is exact at any floor (0 included) and costs no instruction per nonce.
+ *
+ * npow_submit_best returns at once.  Only nonces with value >= floor are candidates; any floor, 0 allowed.  The range
+ * is taken mod 2^64 and split into contiguous parts over the GPUs of device_mask (0 = all) exactly as
+ * npow_submit_sweep splits it; the CPU workers take no part.  The job is a foreground job of weight 1: it takes a
+ * slot, counts against npow_pool_config's limit and queues like a bounded search.  count == 0 completes at once
+ * (NPOW_EXHAUSTED) and touches no device.
+ *
+ * npow_wait_best alone collects such a ticket.  NPOW_PENDING when timeout_us (< 0: none) passes first; the ticket
+ * stays valid.  NPOW_OK: every nonce of the range was hashed exactly once, *value_out is the maximum work value of
+ * the range, *nonce_out the nonce that has it -- among nonces of equal value the one with the smallest nonce - start
+ * -- and *nonces_done (may be null) == count.  NPOW_EXHAUSTED: the range was hashed in full and no value reached
+ * floor; *nonces_done == count.  NPOW_CANCELLED after npow_cancel or *cancel: the best candidate found so far, if
+ * any (*value_out == 0: none), and *nonces_done what was hashed.  The nonce is re-validated on the CPU
+ * (npow_work_value) before it is returned.  A device dropped while it holds the job fails the job with that device's
+ * error, and a launch that recorded more candidates than its records hold (at least 16,384; tens are expected) fails
+ * it with NPOW_ERR_INTERNAL rather than return a possibly wrong answer.  Every status but NPOW_PENDING releases the
+ * ticket.
+ *
+ * npow_cancel works on a best job's ticket.  npow_wait, npow_wait_info, npow_wait_result, npow_wait_sweep,
+ * npow_ticket_sweep, npow_promote, npow_retarget, npow_relax, npow_ticket_reserve and npow_ticket_background return
+ * NPOW_ERR_BAD_ARGUMENT and leave it collectable, as npow_wait_best and npow_ticket_best do for every other kind of
+ * ticket. */
+int npow_submit_best(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count,
+                     uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket);
+int npow_wait_best(uint64_t ticket, int64_t timeout_us, uint64_t* nonce_out, uint64_t* value_out,
+                   uint64_t* nonces_done);
+
+/* A look at an uncollected best ticket (npow_ticket_best). */
+typedef struct npow_best_info {
+  uint32_t size;          /* set by the caller; the library writes at most that many bytes */
+  uint32_t finished;      /* 1: npow_wait_best would return at once */
+  uint64_t count;         /* nonces of the job's range */
+  uint64_t nonces_done;   /* nonces credited by the launches retired so far (the final count once finished) */
+  uint64_t nonce, value;  /* the best candidate of the launches retired so far (value 0: none yet) */
+  uint64_t launches;      /* launches that held an entry of the job, summed over its devices */
+  uint64_t records;       /* candidates those launches recorded, all told ... */
+  uint64_t records_max;   /* ... and the most one launch's entry recorded */
+  uint64_t room;          /* the fewest records one of its entries had room for (0: no launch retired yet) */
+} npow_best_info;
+
+/* Progress of an uncollected best job's ticket (added within ABI 7; probe for the symbol).  Written up to out->size.
+ * NPOW_ERR_BAD_ARGUMENT for any other kind of ticket, an unknown or collected one, or out / out->size missing.  Never
+ * waits for a GPU. */
+int npow_ticket_best(uint64_t ticket, npow_best_info* out);
 
 /* Work values of `count` consecutive nonces start, start+1, ... for one root,
  * computed by the instruction stream the search and sweep kernels execute

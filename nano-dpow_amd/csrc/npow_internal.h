@@ -123,7 +123,10 @@ struct PoolEntry {
                      // Bit 2 (kEntryClaim, with bits 0 and 1): a background sweep job's entry
                      // (npow_submit_sweep_background) -- its workgroups claim chunks of the span from the launch's
                      // claim counter (PoolHits::claim, npow_claims.h) instead of walking the dense mapping, and stop
-                     // claiming at the launch's time budget or a yield
+                     // claiming at the launch's time budget or a yield.  Bit 3 (kEntryBest, with bits 0 and 1, never
+                     // with bit 2): a best job's entry (npow_submit_best) -- `threshold` is the job's best value so
+                     // far, a wave raises its own watch from the launch's best word of the slot (PoolHits::best), and
+                     // only a nonce at or above that word is appended to the entry's region of the records
   uint32_t wsh;      // unbounded: 3 - log2(weight), weight in {1, 2, 4, 8} (npow_submit_weighted): wherever two
                      // entries' workgroup counts are compared, each is shifted left by its wsh first, so a job's
                      // share of the launch's workgroups is weight / (sum of weights).  Equal values compare as the
@@ -235,7 +238,7 @@ constexpr int kPoolRing = 4;  // launch ring of the pool kernels (host: kEventRi
 // entry's region and the shift): a hit lane of slot s stores its nonce at rank n[s]++ of its entry's region, or not
 // at all past the region's end -- the counter keeps counting, so the hit count stays exact.
 constexpr uint32_t kSweepHits = 1u << 20;  // records per set (NPOW_SWEEP_JOB_HITS, include/nanopow.h)
-constexpr uint32_t kEntryBounded = 1u, kEntryCollect = 2u, kEntryClaim = 4u;
+constexpr uint32_t kEntryBounded = 1u, kEntryCollect = 2u, kEntryClaim = 4u, kEntryBest = 8u;
 __host__ __device__ inline uint32_t pool_collect_flags(uint32_t region, uint32_t shift) {
   return kEntryBounded | kEntryCollect | (region << 8) | (shift << 16);
 }
@@ -245,7 +248,10 @@ struct PoolHits {
   unsigned long long n[kMaxSlots];  // hits of the slot's entry in this launch (may exceed its region)
   unsigned long long claim[kMaxSlots];  // chunks claimed of the slot's claimed entry in this launch (kEntryClaim;
                                         // zeroed and read with n; runs past the span's chunks, npow_claims.h)
-  uint64_t rec[kSweepHits];         // the nonces, region by region, each in the order its waves came
+  unsigned long long best[kMaxSlots];   // the highest work value a wave of the slot's best entry has found in this
+                                        // launch (kEntryBest; zeroed with n: a wave's own watch starts at the entry's
+                                        // threshold, so the word needs no seed) -- raised with a device-scope atomic max
+  uint64_t rec[kSweepHits];        // the nonces, region by region, each in the order its waves came
 };
 struct PoolDevState {
   PoolSlotWord slot[kMaxSlots];

@@ -986,21 +986,71 @@ __device__ __noinline__ uint32_t ls2_pick(const PoolTable* tab, PoolDevState* st
 // times that.  Each hit lane then stores its nonce at its rank of the entry's region with a plain vector store, unless
 // the rank is past the region's end -- the counter has counted it all the same, which keeps the hit count exact.  The
 // entry's slot and flags are re-read from it (up points at the entry), as the win path re-reads slot and generation.
-__device__ __forceinline__ void ls2_collect(const PoolTable* tab, PoolDevState* st, const uint64_t* up, uint64_t hits,
-                                            bool hit, uint64_t nonce, uint32_t lane) {
+//
+// Returns the wave's watch threshold from here on: `thr`, the one it came with, for a sweep job's entry.  A best job's
+// entry (kEntryBest, npow_submit_best; the flag is tested here, inside the rare branch, from the re-read flags) goes
+// through ls2_best instead and may come back with a higher one.
+__device__ __forceinline__ uint64_t ls2_best(PoolHits* ph, uint32_t slot, uint32_t region, uint32_t room, uint64_t hits,
+                                             uint64_t value, uint64_t nonce, uint32_t lane);
+__device__ __forceinline__ uint64_t ls2_collect(const PoolTable* tab, PoolDevState* st, const uint64_t* up,
+                                                uint64_t hits, bool hit, uint64_t nonce, uint64_t value, uint64_t thr,
+                                                uint32_t lane) {
   ConstEntry* ce = (ConstEntry*)(uintptr_t)up;
   asm volatile("" : "+s"(ce));
   const uint32_t slot = ce->slot, flags = ce->bounded;
   const uint32_t shift = pool_collect_shift(flags), region = pool_collect_region(flags);
   const uint32_t room = kSweepHits >> shift;
   PoolHits* ph = &st->hits[tab->ring & 1u];
-  if (region >= (1u << shift) || slot >= (uint32_t)kMaxSlots) return;  // (never: the host's table; keeps every index in)
+  if (region >= (1u << shift) || slot >= (uint32_t)kMaxSlots) return thr;  // (never: the host's table; keeps every index in)
+  if (flags & kEntryBest) return ls2_best(ph, slot, region, room, hits, value, nonce, lane);
   unsigned long long first = 0;
   if (lane == 0) first = atomicAdd(&ph->n[slot], (unsigned long long)__builtin_popcountll(hits));
   first = uni64(first);
   const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(hits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hits, 0u));
   const unsigned long long rank = first + below;
   if (hit && rank < room) ph->rec[(size_t)region * room + (size_t)rank] = nonce;
+  return thr;
+}
+
+// A best job's entry (kEntryBest, npow_submit_best: the strongest nonce of a range; pool_body_ls2, BOUNDED only).  The
+// wave's watch is the best value it knows of -- the entry's threshold at first, which the host sets to the job's best
+// so far (its floor before any) -- and `hits` are its lanes at or above the watch, under the bounded lane mask.
+// Its best hit lane (the highest value, and among equal ones the lowest lane: the nonce nearest the range's start) is
+// taken with scalar reads of the lanes; lane 0 raises the launch's best word of the slot with one device-scope atomic
+// max, and when the wave's value is at or above what the word held, appends the nonce to the entry's region of the
+// launch's records (one atomic on the slot's counter and one plain vector store, as a sweep job's hits; past the
+// region's end the counter still counts, and the host then fails the job rather than trust the records).  The wave's
+// watch becomes the larger of its own value and the word's old one.  No win record, no dead word, no stop request.
+//
+// Exact under every interleaving: every watch and the word hold values of the entry's own range or the host's best of
+// the job's earlier ranges, so the watch of the wave that hashes the range's maximum is never above it -- that lane
+// comes here -- and the atomic returns something at or below it: its nonce is appended.  Equal values come here too
+// (>=) and are appended: the host's fold breaks the tie (npow_best.h).  The word starts at zero and needs no seed:
+// nothing below the entry's threshold ever reaches it.
+// Records are rare -- a value is appended only if it is a running maximum of the order the atomics took, about
+// ln(waves) + ln(iterations) per launch -- so this costs no instruction per nonce.
+__device__ __forceinline__ uint64_t ls2_best(PoolHits* ph, uint32_t slot, uint32_t region, uint32_t room, uint64_t hits,
+                                             uint64_t value, uint64_t nonce, uint32_t lane) {
+  const int first = __builtin_ctzll(hits);
+  uint64_t bv = readlane64(value, first), bn = readlane64(nonce, first);
+  for (uint64_t rest = hits & (hits - 1); rest != 0; rest &= rest - 1) {
+    const int l = __builtin_ctzll(rest);
+    const uint64_t cv = readlane64(value, l);
+    if (cv > bv) {
+      bv = cv;
+      bn = readlane64(nonce, l);
+    }
+  }
+  unsigned long long old = 0;
+  if (lane == 0) {
+    old = __hip_atomic_fetch_max(&ph->best[slot], (unsigned long long)bv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (bv >= old) {
+      const unsigned long long rank = atomicAdd(&ph->n[slot], 1ull);
+      if (rank < room) ph->rec[(size_t)region * room + (size_t)rank] = bn;
+    }
+  }
+  old = uni64(old);
+  return bv > old ? bv : old;
 }
 
 // A claimed collecting entry (kEntryClaim: a background sweep job, npow_submit_sweep_background; pool_body_ls2, BOUNDED
@@ -1157,10 +1207,11 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
       // Sweep jobs (npow_submit_sweep; only bounded entries collect, so only the BOUNDED kernels carry this): a
       // collecting entry never wins.  Its hit lanes (under the bounded lane mask above) append their nonces to the
       // entry's region of the launch's hit records and the wave goes on with no hit left: no win record, no dead
-      // word, no stop request, no floor and no reserve.
+      // word, no stop request, no floor and no reserve.  A best job's entry (npow_submit_best) collects too, but only
+      // what beats the launch's best so far, and its wave's watch threshold rises with it (ls2_best).
       if constexpr (BOUNDED) {
         if (__builtin_expect(hits != 0, 0) && (c.bounded & kEntryCollect)) {
-          ls2_collect(tab, st, c.up, hits, hit, nonce, lane);
+          c.threshold = ls2_collect(tab, st, c.up, hits, hit, nonce, value, thr, lane);
           hits = 0;
         }
       }

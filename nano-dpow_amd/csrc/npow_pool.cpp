@@ -33,6 +33,11 @@
 // (kEntryClaim): a launch covers a prefix of its span, told by its claim counter, and ends at the time budget or a
 // yield; collect_hits credits the prefix and hands the rest back.  DESIGN.md section 1 "Background sweep jobs".
 //
+// A best job (npow_submit_best; Job::sweep with Job::best) is a foreground sweep job whose entries (kEntryBest) keep
+// only the nonces that beat the best value their launch has seen: collect_hits recomputes each record's value on the
+// CPU and folds it into the job's best (npow_best.h), which the next entry carries as its watch; pool_wait_best
+// returns it.  DESIGN.md section 1 "Best jobs".
+//
 // Threads: one persistent worker per device (started by npow_init) owns the device's
 // stream, its slot table and up to two launches in flight (the second is queued only near
 // the end of the first one's budget, or at once behind a launch with no live entry left);
@@ -1041,9 +1046,12 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
       const std::deque<Range>& todo = j.dev[sl.k].todo;
       if (j.sweep) {
         // the span a bounded job takes, unless the threshold is so low that its hits would not fit the region
+        // (a best job's records are rare whatever its floor: the bounded span, and its best so far as the watch)
         const uint32_t room = kSweepHits >> cshift, region = (uint32_t)collect_.size();
-        take_entry(sl, t.e[e], std::min(sh.own(e, n, iters), collect_span(j.threshold, room)), seq_, t_issue);
-        t.e[e].bounded = pool_collect_flags(region, cshift) | (j.claimed() ? kEntryClaim : 0u);
+        const uint64_t span = j.best ? ~0ull : collect_span(j.threshold, room);
+        take_entry(sl, t.e[e], std::min(sh.own(e, n, iters), span), seq_, t_issue);
+        if (j.best) t.e[e].threshold = t.e[e].reserve = best_watch(j.best_of, j.threshold);
+        t.e[e].bounded = pool_collect_flags(region, cshift) | (j.claimed() ? kEntryClaim : 0u) | (j.best ? kEntryBest : 0u);
         t.e[e].wsh = pool_wsh(j.weight);
         weights[e] = j.weight;
         bgs[e] = 0;
@@ -1161,7 +1169,7 @@ int Worker::launch(bool empty_linger) {
   // Sweep jobs: this launch's set of hit records (PoolHits) starts from zero counts, in stream order.  Its previous
   // user, the launch before the last, has retired -- at most two are in flight -- and its hits were read then.
   if (!collect_.empty())
-    HIPTRY(hipMemsetAsync(&d_.pst->hits[r & 1], 0, offsetof(PoolHits, rec), d_.stream));  // (n and claim)
+    HIPTRY(hipMemsetAsync(&d_.pst->hits[r & 1], 0, offsetof(PoolHits, rec), d_.stream));  // (n, claim and best)
   if (n <= (uint32_t)kArgEntries) {
     HIPTRY(hipEventRecord(d_.ev_start[r], d_.stream));
     HIPTRY(launch_pool_arg(d_.stream, sh.grid, t, bounded, d_.pst, d_.pmb_dev));
@@ -1251,8 +1259,8 @@ int Worker::collect_hits(const PoolInflight& f) {
   if (f.collect.empty()) return NPOW_OK;
   DEVCHECK(d_, "pool hit read-back");
   PoolHits* set = &d_.pst->hits[f.ring & 1];
-  static_assert(offsetof(PoolHits, claim) == sizeof(PoolHits::n) && offsetof(PoolHits, rec) == 2 * sizeof(PoolHits::n),
-                "the hit and claim counters are read with one copy");
+  static_assert(offsetof(PoolHits, claim) == sizeof(PoolHits::n) && offsetof(PoolHits, rec) == 3 * sizeof(PoolHits::n),
+                "the hit and claim counters (and the best words behind them) are read with one copy");
   HIPTRY(hipMemcpyAsync(d_.h_hit_n, set, offsetof(PoolHits, rec), hipMemcpyDeviceToHost, d_.hit_stream));
   HIPTRY(hipStreamSynchronize(d_.hit_stream));
   for (const PoolInflight::Collect& c : f.collect) {
@@ -1266,6 +1274,39 @@ int Worker::collect_hits(const PoolInflight& f) {
       HIPTRY(hipStreamSynchronize(d_.hit_stream));
     }
     const uint64_t start = sl.job->start;
+    if (sl.job->best) {
+      // A best job: the launch's records are the nonces that beat the launch's best as their waves came (ls2_best),
+      // the span's maximum among them.  Each value is recomputed here, on the CPU, and nothing else of the record is
+      // trusted; a nonce outside the entry's span, or more records than the region holds (the maximum may be among
+      // the lost ones), fails the job -- it never returns a possibly wrong answer.
+      Job& j = *sl.job;
+      std::vector<uint64_t> values(stored);
+      bool outside = false;
+      for (uint64_t i = 0; i < stored; ++i) {
+        outside = outside || d_.h_hits[i] - c.base >= c.count;
+        values[i] = host_work_value(j.pre.m, d_.h_hits[i]);
+      }
+      std::lock_guard<std::mutex> g(g_pool.mu);
+      JobDev& jd = j.dev[sl.k];
+      jd.hit_n += n;
+      jd.launches++;
+      j.best_records += n;
+      j.best_records_max = std::max(j.best_records_max, n);
+      j.best_room = j.best_room ? std::min<uint64_t>(j.best_room, c.room) : c.room;
+      if ((outside || n > stored) && !j.decided) {
+        j.err = "best job: device " + std::to_string(d_.id) +
+                (outside ? " recorded a nonce outside its launch's span"
+                         : " appended " + std::to_string(n) + " records where its region holds " + std::to_string(c.room));
+        decide_locked(j, NPOW_ERR_INTERNAL);
+        g_pool.decisions.fetch_add(1, std::memory_order_release);
+        notify_workers_locked();
+        continue;
+      }
+      const uint64_t floor = j.threshold.load(std::memory_order_relaxed);
+      for (uint64_t i = 0; i < stored && !outside; ++i) best_fold(j.best_of, start, floor, d_.h_hits[i], values[i]);
+      if (sl.stop_us == 0 && !j.decided.load()) jd.progress += c.count;
+      continue;
+    }
     std::sort(d_.h_hits, d_.h_hits + stored, [start](uint64_t x, uint64_t y) { return x - start < y - start; });
     std::lock_guard<std::mutex> g(g_pool.mu);
     JobDev& jd = sl.job->dev[sl.k];
@@ -1869,6 +1910,8 @@ static JobP find_ticket(uint64_t ticket) {
 // call on it is refused and leaves it as it was (Job::sweep does not change after the submit: no lock needed).
 static int refuse_sweep(const Job& j, const char* call) {
   if (!j.sweep) return NPOW_OK;
+  if (j.best)
+    return fail(NPOW_ERR_BAD_ARGUMENT, std::string(call) + ": the ticket is a best job's (npow_wait_best collects it)");
   return fail(NPOW_ERR_BAD_ARGUMENT, std::string(call) + ": the ticket is a sweep job's (npow_wait_sweep collects it)");
 }
 
@@ -2152,9 +2195,10 @@ int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered) {
 // GPUs of the mask, as npow_sweep splits it (a GPU whose part would be empty is left out); each worker reads its
 // launches' hits as they retire (collect_hits), and pool_wait_sweep merges the devices' lists.
 int pool_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count, uint64_t device_mask,
-                      const volatile uint32_t* cancel, uint64_t* ticket, bool background) {
+                      const volatile uint32_t* cancel, uint64_t* ticket, bool background, bool best) {
   auto j = std::make_shared<Job>();
   j->sweep = true;
+  j->best = best;  // (npow_submit_best: `threshold` is its floor)
   j->background = background;  // (npow_submit_sweep_background: admitted as a background search is, admit_locked)
   j->count = count;
   j->pre = host_precompute(root);
@@ -2207,6 +2251,7 @@ int pool_ticket_sweep(uint64_t ticket, npow_sweep_info* out) {
   if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
   const Job& j = *it->second;
   if (!j.sweep) return fail(NPOW_ERR_BAD_ARGUMENT, "npow_ticket_sweep: the ticket is a search's");
+  if (j.best) return fail(NPOW_ERR_BAD_ARGUMENT, "npow_ticket_sweep: the ticket is a best job's (npow_ticket_best)");
   const bool fin = j.finished.load();
   const double t = fin ? j.t_finish : now_us();
   out->background = j.background ? 1u : 0u;
@@ -2231,6 +2276,8 @@ int pool_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t
   JobP j = find_ticket(ticket);
   if (!j) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
   if (!j->sweep) return fail(NPOW_ERR_BAD_ARGUMENT, "npow_wait_sweep: the ticket is a search's (npow_wait collects it)");
+  if (j->best)
+    return fail(NPOW_ERR_BAD_ARGUMENT, "npow_wait_sweep: the ticket is a best job's (npow_wait_best collects it)");
   if (wait_job(j, timeout_us, [&] { return j->finished.load(std::memory_order_acquire); }) == NPOW_PENDING)
     return NPOW_PENDING;
   std::unique_lock<std::mutex> lk(g_pool.mu);
@@ -2265,6 +2312,73 @@ int pool_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t
     return fail(NPOW_ERR_CAPACITY, "more than NPOW_SWEEP_JOB_HITS hits on a device (n_out is exact)");
   if (total > cap) return fail(NPOW_ERR_CAPACITY, "more hits than cap");
   return NPOW_OK;
+}
+
+// -- best jobs (npow_submit_best, npow_wait_best) --------------------------------------------------------------------
+// The strongest nonce of [start, start + count): a sweep job's sibling (pool_submit_sweep with `best`: the same split,
+// admission and queue) whose entries keep only what beats the best so far (kEntryBest).  The workers fold each retired
+// launch's records into Job::best_of (collect_hits); this only reads the result.  DESIGN.md section 1 "Best jobs".
+int pool_submit_best(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count, uint64_t device_mask,
+                     const volatile uint32_t* cancel, uint64_t* ticket) {
+  return pool_submit_sweep(root, floor, start, count, device_mask, cancel, ticket, false, true);
+}
+
+static int refuse_not_best(const Job& j, const char* call) {
+  if (j.best) return NPOW_OK;
+  return fail(NPOW_ERR_BAD_ARGUMENT, std::string(call) + (j.sweep ? ": the ticket is a sweep job's (npow_wait_sweep collects it)"
+                                                                  : ": the ticket is a search's (npow_wait collects it)"));
+}
+
+int pool_ticket_best(uint64_t ticket, npow_best_info* out) {
+  std::lock_guard<std::mutex> g(g_pool.mu);
+  auto it = g_pool.tickets.find(ticket);
+  if (it == g_pool.tickets.end()) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  const Job& j = *it->second;
+  if (int rc = refuse_not_best(j, "npow_ticket_best")) return rc;
+  const bool fin = j.finished.load();
+  uint64_t progress = 0;
+  for (const JobDev& jd : j.dev) {
+    progress += jd.progress;
+    out->launches += jd.launches;
+  }
+  out->count = j.count;
+  out->nonces_done = fin ? j.done : std::max(j.done, progress);
+  out->nonce = j.best_of.found ? j.best_of.nonce : 0;
+  out->value = j.best_of.found ? j.best_of.value : 0;
+  out->records = j.best_records;
+  out->records_max = j.best_records_max;
+  out->room = j.best_room;
+  out->finished = fin ? 1u : 0u;
+  return NPOW_OK;
+}
+
+int pool_wait_best(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* value, uint64_t* nonces_done) {
+  JobP j = find_ticket(ticket);
+  if (!j) return fail(NPOW_ERR_BAD_ARGUMENT, "unknown ticket");
+  if (int rc = refuse_not_best(*j, "npow_wait_best")) return rc;
+  if (wait_job(j, timeout_us, [&] { return j->finished.load(std::memory_order_acquire); }) == NPOW_PENDING)
+    return NPOW_PENDING;
+  std::unique_lock<std::mutex> lk(g_pool.mu);
+  g_pool.tickets.erase(ticket);
+  const BestFold b = j->best_of;
+  const uint64_t done = j->done;
+  const int st = j->status;
+  lk.unlock();
+  if (nonces_done) *nonces_done = done;
+  if (nonce) *nonce = 0;
+  if (value) *value = 0;
+  if (st < 0) return fail(st, j->err.empty() ? std::string("best job failed") : j->err);
+  if (st != NPOW_CANCELLED && done != j->count)
+    return fail(NPOW_ERR_INTERNAL, "best job: hashed " + std::to_string(done) + " nonces of " + std::to_string(j->count));
+  if (b.found) {
+    // (each record was recomputed when it was folded; once more, as every winner is before it is returned)
+    if (host_work_value(j->pre.m, b.nonce) != b.value || b.nonce - j->start >= j->count)
+      return fail(NPOW_ERR_INTERNAL, "best job: the best nonce failed re-validation");
+    if (nonce) *nonce = b.nonce;
+    if (value) *value = b.value;
+  }
+  if (st == NPOW_CANCELLED) return NPOW_CANCELLED;
+  return b.found ? NPOW_OK : NPOW_EXHAUSTED;
 }
 
 int pool_set_max_active(uint32_t n) {

@@ -12,6 +12,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "npow_best.h"
 #include "npow_host.h"
 
 namespace npow {
@@ -80,6 +81,16 @@ struct Job {
   // there (Worker::hold_out).
   bool sweep = false;
   bool claimed() const { return sweep && background; }
+  // A best job (npow_submit_best; `sweep` is set too, `background` never): a sweep job's sibling whose entries keep
+  // only what beats the best value so far (PoolEntry::bounded kEntryBest).  Same admission, parts, range queues and
+  // retirement; its launches' few records are validated on the CPU and folded into `best_of` as they retire
+  // (Worker::collect_hits, npow_best.h), and each new entry carries best_watch() as its threshold.  `threshold` holds
+  // the floor.  Only pool_wait_best collects its ticket.  All guarded by g_pool.mu (`best` never changes).
+  bool best = false;
+  BestFold best_of;
+  uint64_t best_records = 0;      // records read from its retired launches, and ...
+  uint64_t best_records_max = 0;  // ... the most one launch's entry appended (npow_ticket_best)
+  uint64_t best_room = 0;         // the smallest region one of its entries had (records; 0 = no launch yet)
   uint64_t count = 0;
   uint64_t start = 0, max_per_dev = 0, spacing = 0;
   const volatile uint32_t* cancel = nullptr;

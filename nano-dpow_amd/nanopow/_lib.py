@@ -53,7 +53,7 @@ EXPORTED_SYMBOLS = (
     "npow_abi_version", "npow_config_cpu_threads", "npow_wait_result", "npow_submit_weighted",
     "npow_promote", "npow_retarget", "npow_submit_background", "npow_ticket_background",
     "npow_submit_reserve", "npow_ticket_reserve", "npow_relax", "npow_submit_sweep", "npow_wait_sweep",
-    "npow_submit_sweep_background", "npow_ticket_sweep",
+    "npow_submit_sweep_background", "npow_ticket_sweep", "npow_submit_best", "npow_wait_best", "npow_ticket_best",
 )
 
 
@@ -170,6 +170,47 @@ class SweepInfo:
     launches_cut: int      # of those, launches a yield or the time budget ended before their span was hashed
     held_us: int           # time the job sat admitted but left out of its devices' tables
     finished: bool         # wait() would return at once
+
+
+class _BestInfoStruct(ctypes.Structure):
+    """npow_best_info as the C ABI lays it out (npow_ticket_best)."""
+    _fields_ = [
+        ("size", ctypes.c_uint32),
+        ("finished", ctypes.c_uint32),
+        ("count", ctypes.c_uint64),
+        ("nonces_done", ctypes.c_uint64),
+        ("nonce", ctypes.c_uint64),
+        ("value", ctypes.c_uint64),
+        ("launches", ctypes.c_uint64),
+        ("records", ctypes.c_uint64),
+        ("records_max", ctypes.c_uint64),
+        ("room", ctypes.c_uint64),
+    ]
+
+
+@dataclass
+class BestInfo:
+    """A look at an uncollected best job (BestTicket.info, npow_ticket_best)."""
+    finished: bool         # wait() would return at once
+    count: int             # nonces of the range
+    nonces_done: int       # credited by the launches retired so far
+    nonce: int             # the best candidate of the launches retired so far ...
+    value: int             # ... and its work value (0: none yet)
+    launches: int          # launches that held an entry of the job, summed over its devices
+    records: int           # candidates those launches recorded, all told
+    records_max: int       # the most one launch's entry recorded
+    room: int              # the fewest records one of its entries had room for (0: no launch retired yet)
+
+
+@dataclass
+class BestResult:
+    status: int            # NPOW_OK / NPOW_EXHAUSTED (nothing reached the floor) / NPOW_CANCELLED
+    nonce: Optional[int]   # the range's strongest nonce (cancelled: the best found so far; None: none)
+    value: Optional[int]
+    nonces_done: int       # == count unless cancelled
+
+    def __iter__(self):    # status, nonce, value, nonces_done = ticket.wait()
+        return iter((self.status, self.nonce, self.value, self.nonces_done))
 
 
 @dataclass
@@ -292,6 +333,13 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.npow_submit_sweep_background.restype = ctypes.c_int
             lib.npow_ticket_sweep.argtypes = [u64, ctypes.POINTER(_SweepInfoStruct)]
             lib.npow_ticket_sweep.restype = ctypes.c_int
+        if hasattr(lib, "npow_submit_best"):  # added within ABI 7: probed for
+            lib.npow_submit_best.argtypes = [u8p, u64, u64, u64, u64, p, pu64]
+            lib.npow_submit_best.restype = ctypes.c_int
+            lib.npow_wait_best.argtypes = [u64, ctypes.c_int64, pu64, pu64, pu64]
+            lib.npow_wait_best.restype = ctypes.c_int
+            lib.npow_ticket_best.argtypes = [u64, ctypes.POINTER(_BestInfoStruct)]
+            lib.npow_ticket_best.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -560,6 +608,66 @@ class SweepTicket:
             pass
 
 
+class BestTicket:
+    """A submitted best job (npow_submit_best); wait() returns its BestResult once."""
+
+    def __init__(self, engine: "Engine", ticket: int, cancel: Optional[CancelToken]) -> None:
+        self.engine = engine
+        self.ticket = ticket
+        self.cancel_token = cancel  # keeps the cancel word alive while the engine may read it
+        self.result: Optional[BestResult] = None
+
+    def wait(self, timeout: Optional[float] = None) -> Optional[BestResult]:
+        """Block until the job ends (timeout None) or up to `timeout` seconds; None if it is still running then.
+        The result unpacks as status, nonce, value, nonces_done.  NPOW_OK: the range's strongest nonce and its work
+        value, nonces_done == count; NPOW_EXHAUSTED: nothing reached the floor; NPOW_CANCELLED: the best found so
+        far (nonce None: none); an error raises."""
+        if self.result is not None:
+            return self.result
+        lib = self.engine.lib
+        nonce, value, done = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        us = -1 if timeout is None else max(0, int(timeout * 1e6))
+        rc = lib.npow_wait_best(self.ticket, us, ctypes.byref(nonce), ctypes.byref(value), ctypes.byref(done))
+        if rc == NPOW_PENDING:
+            return None
+        self.cancel_token = None
+        self.ticket = 0  # collected, whatever the status
+        _check(rc, lib, ok=(NPOW_OK, NPOW_CANCELLED, NPOW_EXHAUSTED))
+        found = rc == NPOW_OK or (rc == NPOW_CANCELLED and value.value != 0)
+        self.result = BestResult(rc, nonce.value if found else None, value.value if found else None, done.value)
+        return self.result
+
+    def info(self) -> BestInfo:
+        """The job's progress and best candidate so far (npow_ticket_best); never waits for a GPU.
+        NanoPowError(NPOW_ERR_BAD_ARGUMENT) once the ticket is collected."""
+        lib = self.engine.lib
+        if not self.ticket:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the best ticket is collected")
+        i = _BestInfoStruct()
+        i.size = ctypes.sizeof(_BestInfoStruct)
+        _check(lib.npow_ticket_best(self.ticket, ctypes.byref(i)), lib)
+        return BestInfo(bool(i.finished), i.count, i.nonces_done, i.nonce, i.value, i.launches, i.records,
+                        i.records_max, i.room)
+
+    def cancel(self) -> None:
+        if self.result is None and self.ticket:
+            _check(self.engine.lib.npow_cancel(self.ticket), self.engine.lib)
+
+    def __del__(self) -> None:
+        # An abandoned ticket: as Ticket.__del__ -- cancel the job and collect it, so the engine forgets it and
+        # stops reading the cancel word before that word is freed.
+        if self.result is not None or not getattr(self, "ticket", 0):
+            return
+        try:
+            lib = self.engine.lib
+            lib.npow_cancel(self.ticket)
+            n, v = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            if lib.npow_wait_best(self.ticket, 10_000_000, ctypes.byref(n), ctypes.byref(v), None) == NPOW_PENDING:
+                _ORPHANED_CANCEL_WORDS.append(self.cancel_token)
+        except Exception:  # interpreter shutdown: the library may already be gone
+            pass
+
+
 class Engine:
     """Thin object wrapper over the C ABI (one per process is enough)."""
 
@@ -716,6 +824,20 @@ class Engine:
         _check(getattr(self.lib, name)(_root(root), threshold & M64, start & M64, count, device_mask,
                                        cancel.address if cancel else None, ctypes.byref(t)), self.lib)
         return SweepTicket(self, t.value, cancel, cap)
+
+    def submit_best(self, root: bytes, start: int, count: int, floor: int = 0, device_mask: int = 0,
+                    cancel: Optional[CancelToken] = None) -> BestTicket:
+        """Queue a best job and return at once (npow_submit_best): the nonce of [start, start + count) with the
+        highest work value, found inside the work pool's launches beside the live searches -- exact at any floor
+        (only values >= floor are candidates; 0 allowed).  BestTicket.wait gives status, nonce, value, nonces_done.
+        Keep `cancel` alive until then (the ticket holds a reference).  NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the
+        loaded library lacks the call."""
+        if not hasattr(self.lib, "npow_submit_best"):
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_submit_best")
+        t = ctypes.c_uint64(0)
+        _check(self.lib.npow_submit_best(_root(root), floor & M64, start & M64, count, device_mask,
+                                         cancel.address if cancel else None, ctypes.byref(t)), self.lib)
+        return BestTicket(self, t.value, cancel)
 
     def sweep(self, root: bytes, threshold: int, start: int, count: int, device_mask: int = 0,
               cap: int = 1 << 16, cancel: Optional[CancelToken] = None) -> List[int]:

@@ -53,6 +53,11 @@ asked for more (the server never lowers a shared search by itself), and
 ``{"action": "work_relax", "hash": ..., "difficulty": ...}`` (or ``"multiplier"``; answered
 ``{}`` like ``work_retarget``) lowers every queued or running search of the hash that is above
 it, in place (npow_relax: decided at once from its reserve when that qualifies).
+``{"action": "work_best", "hash": ..., "count": N}`` (this server's extension; optional
+``"start"``, 16 hex digits, and ``"difficulty"``, a floor) hashes exactly N nonces (at most
+2^40) and answers with the strongest: ``{"work", "difficulty", "multiplier", "hashes"}``
+(npow_submit_best), ``{"error": "Exhausted"}`` when nothing reached the floor, and
+``{"error": "Cancelled"}`` after a ``work_cancel`` of the hash.
 The reference serves one request at a time; here up to ``max_active`` queued
 requests are handed to libnanopow's work pool at once (npow_submit), where
 every selected GPU searches all of them in the same kernel launches, so a
@@ -77,7 +82,8 @@ import time
 from typing import Any, Dict, List, Optional, Protocol
 
 from . import work as W
-from ._lib import NPOW_CANCELLED, NPOW_OK, NPOW_RESERVE_MIN, CancelToken, NanoPowError, SearchResult
+from ._lib import (NPOW_CANCELLED, NPOW_EXHAUSTED, NPOW_OK, NPOW_RESERVE_MIN, CancelToken, NanoPowError,
+                   SearchResult)
 
 log = logging.getLogger("nanopow.server")
 
@@ -154,6 +160,7 @@ class WorkServer:
         self._lock = threading.Condition()
         self._queue: List[Job] = []
         self._inflight: List[Job] = []
+        self._best: List[Any] = []  # work_best requests in the engine: (root, cancel token)
         self._running = False
         # tickets answered at their decision (npow_wait_result) and collected after the reply
         self._reap_q: "queue.SimpleQueue" = queue.SimpleQueue()
@@ -172,6 +179,8 @@ class WorkServer:
             self._queue.clear()
             for j in self._inflight:
                 j.cancel.set()
+            for _, c in self._best:
+                c.set()
             self._lock.notify_all()
         for j in pending:
             j.resolve({"error": "Cancelled"})
@@ -230,6 +239,8 @@ class WorkServer:
                 return self.work_relax(req)
             if action == "work_validate":
                 return self.work_validate(req)
+            if action == "work_best" and hasattr(self.engine, "submit_best"):
+                return self.work_best(req)
             if action == "status":
                 return self.status()
             if action == "benchmark":
@@ -261,6 +272,9 @@ class WorkServer:
             for j in self._inflight:
                 if j.root == root:
                     j.cancel.set()
+            for r, c in self._best:
+                if r == root:
+                    c.set()
         for j in cancelled:
             j.resolve({"error": "Cancelled"})
         log.info("Cancel %s", root.hex().upper())
@@ -388,6 +402,46 @@ class WorkServer:
         log.info("Answered %s from a reserve for difficulty %016x", job.root.hex().upper(), threshold)
         return {"work": W.fmt_u64(res.nonce), "difficulty": W.fmt_u64(value),
                 "multiplier": W.fmt_multiplier(W.to_multiplier(value, self.base))}
+
+    def work_best(self, req: Dict[str, Any]) -> Dict[str, Any]:
+        """The strongest work among exactly `count` nonces of the hash (this server's extension; the engine's best
+        job, npow_submit_best): best-effort work at a cost fixed in advance.  ``"start"`` (16 hex digits; random
+        when absent) is the range's first nonce and ``"difficulty"`` a floor below which nothing is returned
+        (``{"error": "Exhausted"}``).  The job queues in the engine like a bounded search; it is not shared with
+        other requests, and a work_cancel of the hash cancels it."""
+        root = W.parse_hash(req)
+        count = W.parse_best_count(req)
+        start = W.parse_start(req)
+        floor = W.parse_threshold(req["difficulty"]) if req.get("difficulty") is not None else 0
+        if start is None:
+            start = self.rng.getrandbits(64)
+        cancel = CancelToken()
+        entry = (root, cancel)
+        with self._lock:
+            if not self._running:
+                return dict(GENERATION_FAILED)
+            self._best.append(entry)
+        try:
+            t0 = time.perf_counter()
+            ticket = self.engine.submit_best(root, start, count, floor=floor, device_mask=self.device_mask,
+                                             cancel=cancel)
+            status, nonce, value, done = ticket.wait()
+            if status == NPOW_CANCELLED:
+                return {"error": "Cancelled"}
+            if status == NPOW_EXHAUSTED:
+                return {"error": "Exhausted"}
+            if status != NPOW_OK or self.engine.work_value(root, nonce) != value:
+                return dict(GENERATION_FAILED)
+            log.info("Best of %d nonces for %s in %.0fms: difficulty %016x", count, root.hex().upper(),
+                     (time.perf_counter() - t0) * 1000.0, value)
+            return {"work": W.fmt_u64(nonce), "difficulty": W.fmt_u64(value),
+                    "multiplier": W.fmt_multiplier(W.to_multiplier(value, self.base)), "hashes": str(done)}
+        except Exception as e:  # never leave a client waiting
+            log.error("Error computing work: %s", e)
+            return dict(GENERATION_FAILED)
+        finally:
+            with self._lock:
+                self._best.remove(entry)
 
     def work_validate(self, req: Dict[str, Any]) -> Dict[str, Any]:
         root = W.parse_hash(req)

@@ -186,6 +186,38 @@ def parse_count(req: Dict[str, Any]) -> int:
     return c
 
 
+BEST_MAX_COUNT = 1 << 40  # nonces one work_best request may ask for (~40 s of one GPU)
+
+
+def parse_best_count(req: Dict[str, Any]) -> int:
+    """The ``"count"`` of a work_best request (an integer or a decimal string; this server's extension): the nonces
+    to hash, 1 .. 2^40."""
+    if "count" not in req:
+        raise RequestError("Failed to deserialize JSON", "count field missing")
+    c = req["count"]
+    bad = RequestError("Bad count", f"Expecting a positive integer of at most {BEST_MAX_COUNT} for count")
+    if isinstance(c, bool) or not isinstance(c, (int, str)):
+        raise bad
+    if isinstance(c, str):
+        if not (c.isascii() and c.isdigit()) or len(c) > 20:
+            raise bad
+        c = int(c)
+    if not 0 < c <= BEST_MAX_COUNT:
+        raise bad
+    return c
+
+
+def parse_start(req: Dict[str, Any]):
+    """The optional ``"start"`` of a work_best request: the range's first nonce, 16 hex digits like a work value.
+    None when absent."""
+    s = req.get("start")
+    if s is None:
+        return None
+    if not isinstance(s, str) or len(s) != 16 or not _HEX64.fullmatch(s):
+        raise RequestError("Bad start", "Expecting 16 hex digits for start")
+    return int(s, 16)
+
+
 def parse_gpu_spec(spec: str) -> Tuple[int, int, int]:
     """``PLATFORM:DEVICE[:THREADS]`` (nano-work-server.exe @1681064).  HIP has a single
     platform, so PLATFORM is accepted and ignored; THREADS (nonces per launch,
