@@ -175,7 +175,7 @@ std::vector<Device*> select_gpus(uint64_t mask);
 // Per-launch event accounting (kernel time by HIP events on the launch's own stream).
 void account_launch(Device& d, int ring);
 
-// ---- work pool (npow_pool.cpp; npow_pool_watch.cpp: its win watcher) ------------------------------------
+// ---- work pool (npow_pool.cpp; npow_pool_jobs.cpp: its ticket calls; npow_pool_watch.cpp: its win watcher) ----
 bool test_hooks_enabled();          // NANOPOW_TEST_HOOKS=1: the NANOPOW_FAULT_* hooks are honoured
 
 // Device affinity.  Every logical device runs on HIP device hip_id, and its HIP calls must come
@@ -202,6 +202,7 @@ void pool_device_free(Device& d);
 void pool_start();                   // start one worker thread per device
 void pool_stop();                    // stop and join the workers (pending jobs end with an error)
 bool pool_exit();                    // process exit: drain and join the workers (bounded); false: the drain timed out
+// the ticket calls (npow_pool_jobs.cpp)
 int pool_submit(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t device_mask,
                 uint64_t max_nonces_per_device, const volatile uint32_t* cancel, uint64_t* ticket,
                 uint32_t weight = 1,  // weight: 1, 2, 4 or 8 (npow_submit_weighted; checked by the caller)
@@ -221,8 +222,7 @@ int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered);  // npo
 // sweep jobs (npow_submit_sweep, npow_wait_sweep; arguments checked by the caller)
 int pool_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count, uint64_t device_mask,
                       const volatile uint32_t* cancel, uint64_t* ticket,
-                      bool background = false,  // npow_submit_sweep_background
-                      bool best = false);       // pool_submit_best: `threshold` is the floor
+                      bool background = false);  // npow_submit_sweep_background
 // best jobs (npow_submit_best, npow_wait_best, npow_ticket_best; arguments checked by the caller)
 int pool_submit_best(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count, uint64_t device_mask,
                      const volatile uint32_t* cancel, uint64_t* ticket);

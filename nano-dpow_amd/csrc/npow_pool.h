@@ -1,5 +1,6 @@
-// npow_pool.h -- the work pool's jobs and their state transitions (npow_pool.cpp), shared by the GPU workers,
-// the win watcher (npow_pool_watch.cpp) and the CPU workers (npow_cpu.cpp, `--cpu-threads`).
+// npow_pool.h -- the work pool's jobs and their state transitions (npow_pool.cpp), shared by the GPU workers, the
+// ticket calls (npow_pool_jobs.cpp), the win watcher (npow_pool_watch.cpp) and the CPU workers (npow_cpu.cpp,
+// `--cpu-threads`).
 // Internal to libnanopow.so.
 #pragma once
 #include <atomic>
@@ -57,11 +58,13 @@ struct JobDev {
   double held_us = 0, held_since = 0;
 };
 
+enum class JobKind : uint8_t { kSearch, kSweep, kBest };
+
 struct Job {
   uint64_t ticket = 0;
   RootPrecomp pre{};
   uint64_t u[NPOW_ASM_N_UNIFORMS] = {};
-  std::atomic<uint64_t> threshold{0};  // written under g_pool.mu (pool_submit; pool_retarget raises it, pool_relax
+  std::atomic<uint64_t> threshold{0};  // written under g_pool.mu (the submit; pool_retarget raises it, pool_relax
                                        // lowers it, never below `reserve`); the win watcher, the GPU workers and the
                                        // CPU workers read it without the lock
   // Reserve hits (npow_submit_reserve; all guarded by g_pool.mu).  reserve: the reserve threshold, <= threshold at the
@@ -73,24 +76,29 @@ struct Job {
   bool answered = false;            // pool_relax decided the job from its reserve
   uint64_t relaxes = 0;             // lowerings of the threshold that took effect (pool_relax)
   uint64_t candidates = 0;          // reserve records read from the GPUs and validated
+  // The job's kind (set at the submit, never changes: read without the lock).  A search (pool_submit) is decided by
+  // its first win.
   // A sweep job (npow_submit_sweep): a bounded job (max_per_dev != 0: its devices' largest part) that never wins --
   // its entries collect every hit of [start, start + count) (PoolEntry::bounded kEntryCollect, JobDev::hits), each
   // device a contiguous part.  Only pool_wait_sweep collects its ticket; a part is never handed to another device.
   // With `background` set (npow_submit_sweep_background; it never changes: npow_promote refuses the ticket) its entries
   // are claimed ones (kEntryClaim) and a device leaves its slot out of every table built while a foreground job is live
   // there (Worker::hold_out).
-  bool sweep = false;
-  bool claimed() const { return sweep && background; }
-  // A best job (npow_submit_best; `sweep` is set too, `background` never): a sweep job's sibling whose entries keep
-  // only what beats the best value so far (PoolEntry::bounded kEntryBest).  Same admission, parts, range queues and
-  // retirement; its launches' few records are validated on the CPU and folded into `best_of` as they retire
-  // (Worker::collect_hits, npow_best.h), and each new entry carries best_watch() as its threshold.  `threshold` holds
-  // the floor.  Only pool_wait_best collects its ticket.  All guarded by g_pool.mu (`best` never changes).
-  bool best = false;
-  BestFold best_of;
-  uint64_t best_records = 0;      // records read from its retired launches, and ...
-  uint64_t best_records_max = 0;  // ... the most one launch's entry appended (npow_ticket_best)
-  uint64_t best_room = 0;         // the smallest region one of its entries had (records; 0 = no launch yet)
+  // A best job (npow_submit_best; `background` never): a sweep job's sibling whose entries keep only what beats the
+  // best value so far (PoolEntry::bounded kEntryBest).  Same admission, parts, range queues and retirement; its
+  // launches' few records are validated on the CPU and folded into `best.of` as they retire (Worker::collect_best,
+  // npow_best.h), and each new entry carries best_watch() as its threshold.  `threshold` holds the floor.  Only
+  // pool_wait_best collects its ticket.
+  JobKind kind = JobKind::kSearch;
+  bool collects() const { return kind != JobKind::kSearch; }  // its entries collect records: a sweep or a best job
+  bool is_best() const { return kind == JobKind::kBest; }
+  bool claimed() const { return kind == JobKind::kSweep && background; }
+  struct Best {  // a best job's own state (guarded by g_pool.mu)
+    BestFold of;
+    uint64_t records = 0;      // records read from its retired launches, and ...
+    uint64_t records_max = 0;  // ... the most one launch's entry appended (npow_ticket_best)
+    uint64_t room = 0;         // the smallest region one of its entries had (records; 0 = no launch yet)
+  } best;
   uint64_t count = 0;
   uint64_t start = 0, max_per_dev = 0, spacing = 0;
   const volatile uint32_t* cancel = nullptr;

@@ -1,4 +1,4 @@
-// npow_pool_impl.h -- what the work pool's own files share (npow_pool.cpp, npow_pool_watch.cpp;
+// npow_pool_impl.h -- what the work pool's own files share (npow_pool.cpp, npow_pool_jobs.cpp, npow_pool_watch.cpp;
 // nothing else includes it): the environment knobs, the test hooks, the debug prints, the host's writes to a device's
 // pinned mailbox, and the win watcher's interface.
 #pragma once
@@ -45,7 +45,7 @@ inline const bool g_trace_lat = getenv("NANOPOW_TRACE_LATENCY") != nullptr;
 // NANOPOW_TRACE_STEPS=1: each pool worker times the parts of its steps (adopt, check_slots, read-back, launch, retire,
 // nap) and prints count / total / max / calls over 50 us per part when it exits (diagnostics of the host path)
 inline const bool g_trace_steps = getenv("NANOPOW_TRACE_STEPS") != nullptr;
-// NANOPOW_WAIT_SPIN=0: result waiters sleep at once (A/B runs; npow_pool.cpp wait_job)
+// NANOPOW_WAIT_SPIN=0: result waiters sleep at once (A/B runs; npow_pool_jobs.cpp wait_job)
 inline const bool g_wait_spin = env_str("NANOPOW_WAIT_SPIN", "1")[0] != '0';
 
 // Fault injection (tests): see the header comment of npow_pool.cpp.

@@ -381,14 +381,58 @@ class CancelToken:
 _ORPHANED_CANCEL_WORDS: list = []
 
 
-class Ticket:
-    """A submitted search (npow_submit); wait() returns its SearchResult once."""
+class _JobTicket:
+    """What the tickets of the three kinds of pool job share.  Each kind has its wait() and _collect_abandoned(lib): its
+    own wait of up to 10 s, the result thrown away, which returns the status."""
 
     def __init__(self, engine: "Engine", ticket: int, cancel: Optional[CancelToken]) -> None:
         self.engine = engine
         self.ticket = ticket
         self.cancel_token = cancel  # keeps the cancel word alive while the engine may read it
-        self.result: Optional[SearchResult] = None
+        self.result = None
+
+    @staticmethod
+    def _us(timeout: Optional[float]) -> int:
+        return -1 if timeout is None else max(0, int(timeout * 1e6))
+
+    @staticmethod
+    def _need(lib, name: str) -> None:
+        if not hasattr(lib, name):
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, f"the loaded libnanopow has no {name}")
+
+    @staticmethod
+    def _u64(name: str, v) -> None:
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= M64:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, f"{name} must be an integer in [0, 2^64)")
+
+    def _uncollected(self) -> None:
+        if self.result is not None:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
+
+    def cancel(self) -> None:
+        if self.result is None and self.ticket:
+            _check(self.engine.lib.npow_cancel(self.ticket), self.engine.lib)
+
+    def __del__(self) -> None:
+        # An abandoned ticket: cancel its job and collect it, so the engine forgets the job
+        # and stops reading this ticket's cancel word before that word is freed.  A job that
+        # does not end within 10 s keeps its cancel word alive for the life of the process.
+        if self.result is not None or not getattr(self, "ticket", 0):
+            return
+        try:
+            lib = self.engine.lib
+            lib.npow_cancel(self.ticket)
+            if self._collect_abandoned(lib) == NPOW_PENDING:
+                _ORPHANED_CANCEL_WORDS.append(self.cancel_token)
+        except Exception:  # interpreter shutdown: the library may already be gone
+            pass
+
+
+class Ticket(_JobTicket):
+    """A submitted search (npow_submit); wait() returns its SearchResult once."""
+
+    def __init__(self, engine: "Engine", ticket: int, cancel: Optional[CancelToken]) -> None:
+        super().__init__(engine, ticket, cancel)
         self.submitted_background = False  # Engine.submit(background=True): wait_info then reports how it ended
 
     def wait(self, timeout: Optional[float] = None) -> Optional[SearchResult]:
@@ -398,8 +442,7 @@ class Ticket:
             return self.result
         lib = self.engine.lib
         nonce, value, done = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-        us = -1 if timeout is None else max(0, int(timeout * 1e6))
-        rc = lib.npow_wait(self.ticket, us, ctypes.byref(nonce), ctypes.byref(value), ctypes.byref(done))
+        rc = lib.npow_wait(self.ticket, self._us(timeout), ctypes.byref(nonce), ctypes.byref(value), ctypes.byref(done))
         if rc == NPOW_PENDING:
             return None
         self.cancel_token = None
@@ -416,8 +459,7 @@ class Ticket:
             return self.result
         lib = self.engine.lib
         nonce, value = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        us = -1 if timeout is None else max(0, int(timeout * 1e6))
-        rc = lib.npow_wait_result(self.ticket, us, ctypes.byref(nonce), ctypes.byref(value))
+        rc = lib.npow_wait_result(self.ticket, self._us(timeout), ctypes.byref(nonce), ctypes.byref(value))
         if rc == NPOW_PENDING:
             return None
         _check(rc, lib, ok=(NPOW_OK, NPOW_CANCELLED, NPOW_EXHAUSTED))
@@ -433,7 +475,7 @@ class Ticket:
         lib = self.engine.lib
         info = SearchInfo()
         info.size = ctypes.sizeof(SearchInfo)
-        us = -1 if timeout is None else max(0, int(timeout * 1e6))
+        us = self._us(timeout)
         # info.background (a Python attribute: npow_search_info keeps its layout): 1 if the search ended still
         # background.  Only a ticket submitted so can: its class is read once the search is decided (it no longer
         # changes then, npow_ticket_background) and before the ticket is released.
@@ -468,12 +510,10 @@ class Ticket:
         NanoPowError(NPOW_ERR_BAD_ARGUMENT) for another weight, a collected ticket, a bounded search -- and when
         the loaded library has no npow_promote."""
         lib = self.engine.lib
-        if not hasattr(lib, "npow_promote"):
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_promote")
+        self._need(lib, "npow_promote")
         if not isinstance(weight, int) or isinstance(weight, bool) or not 0 <= weight <= 0xffffffff:
             raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "weight must be 1, 2, 4 or 8")
-        if self.result is not None:
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
+        self._uncollected()
         _check(lib.npow_promote(self.ticket, weight), lib)
 
     def retarget(self, threshold: int) -> bool:
@@ -484,12 +524,9 @@ class Ticket:
         cancelled; its result stands).  NanoPowError(NPOW_ERR_BAD_ARGUMENT) for a threshold outside 64 bits, a
         collected ticket -- and when the loaded library has no npow_retarget."""
         lib = self.engine.lib
-        if not hasattr(lib, "npow_retarget"):
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_retarget")
-        if not isinstance(threshold, int) or isinstance(threshold, bool) or not 0 <= threshold <= M64:
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "threshold must be an integer in [0, 2^64)")
-        if self.result is not None:
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
+        self._need(lib, "npow_retarget")
+        self._u64("threshold", threshold)
+        self._uncollected()
         return _check(lib.npow_retarget(self.ticket, threshold), lib, ok=(NPOW_OK, NPOW_TOO_LATE)) == NPOW_OK
 
     def reserve_info(self) -> ReserveInfo:
@@ -497,10 +534,8 @@ class Ticket:
         NanoPowError(NPOW_ERR_BAD_ARGUMENT) for a collected ticket -- and when the loaded library has no
         npow_ticket_reserve."""
         lib = self.engine.lib
-        if not hasattr(lib, "npow_ticket_reserve"):
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_ticket_reserve")
-        if self.result is not None:
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
+        self._need(lib, "npow_ticket_reserve")
+        self._uncollected()
         info = ReserveInfo()
         info.size = ctypes.sizeof(ReserveInfo)
         _check(lib.npow_ticket_reserve(self.ticket, ctypes.byref(info)), lib)
@@ -520,40 +555,23 @@ class Ticket:
         NanoPowError(NPOW_ERR_BAD_ARGUMENT) for a threshold outside 64 bits or below the reserve threshold, a search
         without a reserve, a collected ticket -- and when the loaded library has no npow_relax."""
         lib = self.engine.lib
-        if not hasattr(lib, "npow_relax"):
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_relax")
-        if not isinstance(threshold, int) or isinstance(threshold, bool) or not 0 <= threshold <= M64:
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "threshold must be an integer in [0, 2^64)")
-        if self.result is not None:
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket's result was already collected")
+        self._need(lib, "npow_relax")
+        self._u64("threshold", threshold)
+        self._uncollected()
         answered = ctypes.c_uint32(0)
         rc = _check(lib.npow_relax(self.ticket, threshold, ctypes.byref(answered)), lib, ok=(NPOW_OK, NPOW_TOO_LATE))
         return None if rc == NPOW_TOO_LATE else bool(answered.value)
 
-    def __del__(self) -> None:
-        # An abandoned ticket: cancel its search and collect it, so the engine forgets the job
-        # and stops reading this ticket's cancel word before that word is freed.  A job that
-        # does not end within 10 s keeps its cancel word alive for the life of the process.
-        if self.result is not None or not getattr(self, "ticket", 0):
-            return
-        try:
-            lib = self.engine.lib
-            lib.npow_cancel(self.ticket)
-            if lib.npow_wait(self.ticket, 10_000_000, None, None, None) == NPOW_PENDING:
-                _ORPHANED_CANCEL_WORDS.append(self.cancel_token)
-        except Exception:  # interpreter shutdown: the library may already be gone
-            pass
+    def _collect_abandoned(self, lib) -> int:
+        return lib.npow_wait(self.ticket, 10_000_000, None, None, None)
 
 
-class SweepTicket:
+class SweepTicket(_JobTicket):
     """A submitted sweep job (npow_submit_sweep); wait() returns its SweepResult once."""
 
     def __init__(self, engine: "Engine", ticket: int, cancel: Optional[CancelToken], cap: int) -> None:
-        self.engine = engine
-        self.ticket = ticket
-        self.cancel_token = cancel  # keeps the cancel word alive while the engine may read it
+        super().__init__(engine, ticket, cancel)
         self.cap = cap
-        self.result: Optional[SweepResult] = None
 
     def wait(self, timeout: Optional[float] = None) -> Optional[SweepResult]:
         """Block until the job ends (timeout None) or up to `timeout` seconds; None if it is still running then.
@@ -565,8 +583,8 @@ class SweepTicket:
         lib = self.engine.lib
         out = (ctypes.c_uint64 * max(self.cap, 1))()
         n, done = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        us = -1 if timeout is None else max(0, int(timeout * 1e6))
-        rc = lib.npow_wait_sweep(self.ticket, us, ctypes.addressof(out), self.cap, ctypes.byref(n), ctypes.byref(done))
+        rc = lib.npow_wait_sweep(self.ticket, self._us(timeout), ctypes.addressof(out), self.cap, ctypes.byref(n),
+                                 ctypes.byref(done))
         if rc == NPOW_PENDING:
             return None
         self.cancel_token = None
@@ -579,8 +597,7 @@ class SweepTicket:
         """The job's progress so far (npow_ticket_sweep); never waits for a GPU.  NanoPowError(NPOW_ERR_BAD_ARGUMENT)
         once the ticket is collected, or when the loaded library has no npow_ticket_sweep."""
         lib = self.engine.lib
-        if not hasattr(lib, "npow_ticket_sweep"):
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_ticket_sweep")
+        self._need(lib, "npow_ticket_sweep")
         if not self.ticket:
             raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the sweep ticket is collected")
         i = _SweepInfoStruct()
@@ -589,33 +606,12 @@ class SweepTicket:
         return SweepInfo(bool(i.background), i.count, i.nonces_done, i.hits, i.launches, i.launches_cut, i.held_us,
                          bool(i.finished))
 
-    def cancel(self) -> None:
-        if self.result is None and self.ticket:
-            _check(self.engine.lib.npow_cancel(self.ticket), self.engine.lib)
-
-    def __del__(self) -> None:
-        # An abandoned ticket: as Ticket.__del__ -- cancel the job and collect it, so the engine forgets it and
-        # stops reading the cancel word before that word is freed.
-        if self.result is not None or not getattr(self, "ticket", 0):
-            return
-        try:
-            lib = self.engine.lib
-            lib.npow_cancel(self.ticket)
-            n = ctypes.c_uint64(0)
-            if lib.npow_wait_sweep(self.ticket, 10_000_000, None, 0, ctypes.byref(n), None) == NPOW_PENDING:
-                _ORPHANED_CANCEL_WORDS.append(self.cancel_token)
-        except Exception:  # interpreter shutdown: the library may already be gone
-            pass
+    def _collect_abandoned(self, lib) -> int:
+        return lib.npow_wait_sweep(self.ticket, 10_000_000, None, 0, ctypes.byref(ctypes.c_uint64(0)), None)
 
 
-class BestTicket:
+class BestTicket(_JobTicket):
     """A submitted best job (npow_submit_best); wait() returns its BestResult once."""
-
-    def __init__(self, engine: "Engine", ticket: int, cancel: Optional[CancelToken]) -> None:
-        self.engine = engine
-        self.ticket = ticket
-        self.cancel_token = cancel  # keeps the cancel word alive while the engine may read it
-        self.result: Optional[BestResult] = None
 
     def wait(self, timeout: Optional[float] = None) -> Optional[BestResult]:
         """Block until the job ends (timeout None) or up to `timeout` seconds; None if it is still running then.
@@ -626,8 +622,8 @@ class BestTicket:
             return self.result
         lib = self.engine.lib
         nonce, value, done = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-        us = -1 if timeout is None else max(0, int(timeout * 1e6))
-        rc = lib.npow_wait_best(self.ticket, us, ctypes.byref(nonce), ctypes.byref(value), ctypes.byref(done))
+        rc = lib.npow_wait_best(self.ticket, self._us(timeout), ctypes.byref(nonce), ctypes.byref(value),
+                                ctypes.byref(done))
         if rc == NPOW_PENDING:
             return None
         self.cancel_token = None
@@ -649,23 +645,9 @@ class BestTicket:
         return BestInfo(bool(i.finished), i.count, i.nonces_done, i.nonce, i.value, i.launches, i.records,
                         i.records_max, i.room)
 
-    def cancel(self) -> None:
-        if self.result is None and self.ticket:
-            _check(self.engine.lib.npow_cancel(self.ticket), self.engine.lib)
-
-    def __del__(self) -> None:
-        # An abandoned ticket: as Ticket.__del__ -- cancel the job and collect it, so the engine forgets it and
-        # stops reading the cancel word before that word is freed.
-        if self.result is not None or not getattr(self, "ticket", 0):
-            return
-        try:
-            lib = self.engine.lib
-            lib.npow_cancel(self.ticket)
-            n, v = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            if lib.npow_wait_best(self.ticket, 10_000_000, ctypes.byref(n), ctypes.byref(v), None) == NPOW_PENDING:
-                _ORPHANED_CANCEL_WORDS.append(self.cancel_token)
-        except Exception:  # interpreter shutdown: the library may already be gone
-            pass
+    def _collect_abandoned(self, lib) -> int:
+        n, v = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        return lib.npow_wait_best(self.ticket, 10_000_000, ctypes.byref(n), ctypes.byref(v), None)
 
 
 class Engine:
@@ -723,10 +705,8 @@ class Engine:
         has no npow_submit_reserve, and with max_nonces_per_device."""
         t = ctypes.c_uint64(0)
         if reserve is not None:
-            if not hasattr(self.lib, "npow_submit_reserve"):
-                raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_submit_reserve")
-            if not isinstance(reserve, int) or isinstance(reserve, bool) or not 0 <= reserve <= M64:
-                raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "reserve must be an integer in [0, 2^64)")
+            _JobTicket._need(self.lib, "npow_submit_reserve")
+            _JobTicket._u64("reserve", reserve)
             if not isinstance(weight, int) or isinstance(weight, bool) or not 0 <= weight <= 0xffffffff:
                 raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "weight must be 1, 2, 4 or 8")
             if max_nonces_per_device or (background and weight != 1):
@@ -739,8 +719,7 @@ class Engine:
             tk.submitted_background = bool(background)
             return tk
         if background:
-            if not hasattr(self.lib, "npow_submit_background"):
-                raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_submit_background")
+            _JobTicket._need(self.lib, "npow_submit_background")
             if max_nonces_per_device or weight != 1:
                 raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "a background search is unbounded and has weight 1")
             _check(self.lib.npow_submit_background(_root(root), threshold & M64, start & M64, device_mask,
@@ -818,8 +797,7 @@ class Engine:
         it, and a search that arrives waits one short chunk; continuous foreground load starves the job.
         NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the loaded library lacks the call."""
         name = "npow_submit_sweep_background" if background else "npow_submit_sweep"
-        if not hasattr(self.lib, name):
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, f"the loaded libnanopow has no {name}")
+        _JobTicket._need(self.lib, name)
         t = ctypes.c_uint64(0)
         _check(getattr(self.lib, name)(_root(root), threshold & M64, start & M64, count, device_mask,
                                        cancel.address if cancel else None, ctypes.byref(t)), self.lib)
@@ -832,8 +810,7 @@ class Engine:
         (only values >= floor are candidates; 0 allowed).  BestTicket.wait gives status, nonce, value, nonces_done.
         Keep `cancel` alive until then (the ticket holds a reference).  NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the
         loaded library lacks the call."""
-        if not hasattr(self.lib, "npow_submit_best"):
-            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the loaded libnanopow has no npow_submit_best")
+        _JobTicket._need(self.lib, "npow_submit_best")
         t = ctypes.c_uint64(0)
         _check(self.lib.npow_submit_best(_root(root), floor & M64, start & M64, count, device_mask,
                                          cancel.address if cancel else None, ctypes.byref(t)), self.lib)

@@ -1,7 +1,7 @@
 """The flows of tests/test_gpu_search_positions.py, and that file's child process (the engine reads its environment
 once).  As a program: NANOPOW_VIRTUAL_DEVICES=2, the sole-hit searches (tests/search_positions.py) on CU partition 1
 alone -- its own grid, its own window -- and split over both partitions, where partition 1's stride starts at
-start + 2^63 (npow_pool.cpp pool_submit).  One JSON line on stdout; every check that failed is listed in it."""
+start + 2^63 (npow_pool_jobs.cpp pool_submit).  One JSON line on stdout; every check that failed is listed in it."""
 import contextlib
 import json
 import os

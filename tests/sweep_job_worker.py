@@ -1,7 +1,7 @@
 """Child process of tests/test_gpu_sweep_jobs.py: one sweep job split over G CU partitions.  Run with
 NANOPOW_VIRTUAL_DEVICES=G (G logical devices over the one physical GPU, each with its own stream, hit
 records and worker): npow_submit_sweep of [start, start + 2^22 + 3) at ffff000000000000 over every device
--- contiguous parts that differ in length by one (npow_pool.cpp pool_submit_sweep), so hits lie on both
+-- contiguous parts that differ in length by one (npow_pool_jobs.cpp submit_collecting), so hits lie on both
 sides of every boundary the split cuts.  The merged hit set must equal the C oracle's and the devices'
 nonce counters must add up to the range, each device holding its part.  Prints one JSON line; exits
 non-zero on any mismatch."""

@@ -49,7 +49,8 @@ static const uint64_t g_mask = [] {
   return e ? std::strtoull(e, nullptr, 0) : 1ull;
 }();
 // The bounded ranges name every device explicitly when DRIVER_MASK is 0: mask 0 leaves the CPU workers out of a
-// bounded search (npow_pool.cpp pool_submit), and these runs are to cover them too.  Set in main() after npow_init.
+// bounded search (npow_pool_jobs.cpp pool_submit), and these runs are to cover them too.  Set in main() after
+// npow_init.
 static uint64_t g_bounded_mask = 1;
 
 // first-win searches at an easy threshold, re-validated on the CPU
