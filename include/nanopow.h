@@ -78,7 +78,8 @@ extern "C" {
  * npow_ticket_reserve (a look at that nonce) and npow_relax (lower the threshold of a running search, answered at once
  * from the reserve when it qualifies), with NPOW_RESERVE_MIN and npow_reserve_info; the sweep jobs
  * (npow_submit_sweep, npow_wait_sweep, npow_submit_sweep_background, npow_ticket_sweep) and the best jobs
- * (npow_submit_best, npow_wait_best, npow_ticket_best: the strongest nonce of a range), each described at its
+ * (npow_submit_best, npow_wait_best, npow_ticket_best, npow_submit_best_background, npow_ticket_best_hold: the
+ * strongest nonce of a range), each described at its
  * declaration. */
 #define NPOW_ABI_VERSION 7
 
@@ -519,6 +520,46 @@ typedef struct npow_best_info {
  * NPOW_ERR_BAD_ARGUMENT for any other kind of ticket, an unknown or collected one, or out / out->size missing.  Never
  * waits for a GPU. */
 int npow_ticket_best(uint64_t ticket, npow_best_info* out);
+
+/* Background best jobs (added within ABI 7; probe for the symbols): a best job that each GPU hashes only while no
+ * foreground job wants that GPU -- the class npow_submit_sweep_background gives a sweep job, for the strongest nonce:
+ * strengthen the work held for a root with whatever the GPUs have left, and look at the best so far at any time
+ * (npow_ticket_best).  Same arguments and same split of the range as npow_submit_best; npow_wait_best,
+ * npow_ticket_best and npow_cancel work on the ticket exactly as on a plain best job's, with the same statuses and
+ * guarantees (NPOW_OK: every nonce hashed exactly once, the maximum of the range, the smallest nonce - start among
+ * equal values, *nonces_done == count; NPOW_EXHAUSTED: nothing reached floor; NPOW_CANCELLED: the best candidate so
+ * far and what was hashed; the nonce re-validated on the CPU; NPOW_ERR_INTERNAL rather than a possibly wrong answer;
+ * a dropped device fails the job).  Every other ticket call refuses it as it refuses any best ticket,
+ * npow_ticket_sweep and npow_promote included (a background best job cannot be lifted to a foreground one).
+ * count == 0 completes at once (NPOW_EXHAUSTED).
+ *
+ * On each device the job's part is hashed only in launches built while no foreground job is live on that device or
+ * waiting for it: searches from every other submit call, bounded searches, plain sweep jobs and plain best jobs are
+ * foreground; background searches and background sweep jobs are not, and share a launch with the job.  While held out
+ * the job keeps its slot, its generation, its place in the range and its best so far.  A launch that holds it takes
+ * its span in chunks of 8,192 nonces per workgroup and ends within one chunk (~0.3 ms) once a foreground job arrives
+ * or the launch's time budget (npow_set_pool_tuning) passes; what it did not reach goes back to the job, and what it
+ * found stays a candidate.  It is admitted as background searches are: behind every waiting foreground job, under
+ * the same cap on slots (at most half of them).
+ * CONTINUOUS FOREGROUND LOAD STARVES IT: the job makes no progress while any foreground job is live on its devices,
+ * for as long as that lasts.  That is the meaning of the class. */
+int npow_submit_best_background(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count,
+                                uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket);
+
+/* What its class cost an uncollected best job (npow_ticket_best_hold); npow_best_info keeps its size. */
+typedef struct npow_best_hold_info {
+  uint32_t size;          /* set by the caller; the library writes at most that many bytes */
+  uint32_t background;    /* 1: npow_submit_best_background */
+  uint64_t launches_cut;  /* launches that ended with part of their span unhashed: a yield or the time budget (the
+                           * part went back to the job) */
+  uint64_t held_us;       /* time the job sat admitted but left out of its devices' tables, summed over its devices */
+} npow_best_hold_info;
+
+/* The class of an uncollected best job's ticket, plain or background, and the launches cut and time held that came
+ * with it (added within ABI 7; probe for the symbol); a plain best job reads 0, 0, 0.  Written up to out->size.
+ * NPOW_ERR_BAD_ARGUMENT for any other kind of ticket, an unknown or collected one, or out / out->size missing.  Never
+ * waits for a GPU. */
+int npow_ticket_best_hold(uint64_t ticket, npow_best_hold_info* out);
 
 /* Work values of `count` consecutive nonces start, start+1, ... for one root,
  * computed by the instruction stream the search and sweep kernels execute

@@ -860,6 +860,26 @@ int npow_ticket_best(uint64_t ticket, npow_best_info* out) try {
   return NPOW_OK;
 } catch (...) { return guard_exception(); }
 
+int npow_submit_best_background(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count,
+                                uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket) try {
+  if (int rc = check_init()) return rc;
+  if (!root || !ticket) return fail(NPOW_ERR_BAD_ARGUMENT, "root and ticket are required");
+  return pool_submit_best(root, floor, start, count, device_mask, cancel, ticket, true);
+} catch (...) { return guard_exception(); }
+
+int npow_ticket_best_hold(uint64_t ticket, npow_best_hold_info* out) try {
+  if (int rc = check_init()) return rc;
+  if (!out || out->size < offsetof(npow_best_hold_info, launches_cut))
+    return fail(NPOW_ERR_BAD_ARGUMENT, "out with out->size set is required");
+  npow_best_hold_info full{};
+  const int rc = pool_ticket_best_hold(ticket, &full);
+  if (rc != NPOW_OK) return rc;
+  const uint32_t n = std::min<uint32_t>(out->size, (uint32_t)sizeof(full));
+  full.size = n;
+  memcpy(out, &full, n);
+  return NPOW_OK;
+} catch (...) { return guard_exception(); }
+
 int npow_pool_config(uint32_t max_active) try {
   if (int rc = check_init()) return rc;
   return pool_set_max_active(max_active);

@@ -225,8 +225,10 @@ int pool_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start
                       bool background = false);  // npow_submit_sweep_background
 // best jobs (npow_submit_best, npow_wait_best, npow_ticket_best; arguments checked by the caller)
 int pool_submit_best(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count, uint64_t device_mask,
-                     const volatile uint32_t* cancel, uint64_t* ticket);
+                     const volatile uint32_t* cancel, uint64_t* ticket,
+                     bool background = false);  // npow_submit_best_background
 int pool_ticket_best(uint64_t ticket, npow_best_info* out);  // (out: a full struct, zeroed)
+int pool_ticket_best_hold(uint64_t ticket, npow_best_hold_info* out);  // npow_ticket_best_hold (out: the same)
 int pool_wait_best(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* value, uint64_t* nonces_done);
 int pool_ticket_sweep(uint64_t ticket, npow_sweep_info* out);  // npow_ticket_sweep (out: a full struct)
 int pool_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t cap, uint64_t* n_out,

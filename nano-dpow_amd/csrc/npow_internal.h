@@ -105,7 +105,8 @@ constexpr int kPoolDoneShards = 32;
 //    workgroups (g % n == e, rank r = g / n, k_e of them) run it, index = (it * 8 k_e + 8 r +
 //    wave) * 64 + lane (8 = kLsWaves), dense over [0, count) with count <= 8 k_e * iters * 64; others never
 //    enter it;
-//  * claimed (kEntryClaim, a background sweep job's: bounded and collecting too): the same workgroups, but each takes
+//  * claimed (kEntryClaim, a background sweep or best job's: bounded and collecting too): the same workgroups, but
+//    each takes
 //    chunks of kClaimRows rows from the launch's claim counter of the slot -- chunk c, row r of it, index =
 //    ((c * kClaimRows + r) * 8 + wave) * 64 + lane (npow_claims.h) -- and the launch covers the first `claims` chunks
 //    of [0, count): all of them unless its time budget or a yield stopped the claims.
@@ -120,13 +121,16 @@ struct PoolEntry {
                      // (kEntryCollect, with bit 0): a sweep job's entry (npow_submit_sweep) -- it never wins, every
                      // lane at or above the threshold is appended to the launch's hit records (PoolHits); bits 8..15:
                      // the entry's region of the records, bits 16..20: the regions' size as a shift (pool_collect_*).
-                     // Bit 2 (kEntryClaim, with bits 0 and 1): a background sweep job's entry
-                     // (npow_submit_sweep_background) -- its workgroups claim chunks of the span from the launch's
-                     // claim counter (PoolHits::claim, npow_claims.h) instead of walking the dense mapping, and stop
-                     // claiming at the launch's time budget or a yield.  Bit 3 (kEntryBest, with bits 0 and 1, never
-                     // with bit 2): a best job's entry (npow_submit_best) -- `threshold` is the job's best value so
-                     // far, a wave raises its own watch from the launch's best word of the slot (PoolHits::best), and
-                     // only a nonce at or above that word is appended to the entry's region of the records
+                     // Bit 2 (kEntryClaim, with bits 0 and 1): a background job's entry
+                     // (npow_submit_sweep_background, npow_submit_best_background) -- its workgroups claim chunks of
+                     // the span from the launch's claim counter (PoolHits::claim, npow_claims.h) instead of walking
+                     // the dense mapping, and stop claiming at the launch's time budget or a yield.  Bit 3
+                     // (kEntryBest, with bits 0 and 1): a best job's entry (npow_submit_best) -- `threshold` is the
+                     // job's best value so far, a wave raises its own watch from the launch's best word of the slot
+                     // (PoolHits::best), and only a nonce at or above that word is appended to the entry's region of
+                     // the records.  Bits 2 and 3 together: a background best job's entry -- the chunks decide which
+                     // nonces a workgroup hashes, the best branch what it records; a wave's watch carries from one
+                     // claimed chunk to the next
   uint32_t wsh;      // unbounded: 3 - log2(weight), weight in {1, 2, 4, 8} (npow_submit_weighted): wherever two
                      // entries' workgroup counts are compared, each is shifted left by its wsh first, so a job's
                      // share of the launch's workgroups is weight / (sum of weights).  Equal values compare as the
@@ -249,8 +253,9 @@ struct PoolHits {
   unsigned long long claim[kMaxSlots];  // chunks claimed of the slot's claimed entry in this launch (kEntryClaim;
                                         // zeroed and read with n; runs past the span's chunks, npow_claims.h)
   unsigned long long best[kMaxSlots];   // the highest work value a wave of the slot's best entry has found in this
-                                        // launch (kEntryBest; zeroed with n: a wave's own watch starts at the entry's
-                                        // threshold, so the word needs no seed) -- raised with a device-scope atomic max
+                                        // launch (kEntryBest; zeroed with n and claim, one launch's all three: a
+                                        // wave's own watch starts at the entry's threshold, so the word needs no
+                                        // seed) -- raised with a device-scope atomic max
   uint64_t rec[kSweepHits];        // the nonces, region by region, each in the order its waves came
 };
 struct PoolDevState {

@@ -1029,6 +1029,13 @@ __device__ __forceinline__ uint64_t ls2_collect(const PoolTable* tab, PoolDevSta
 // nothing below the entry's threshold ever reaches it.
 // Records are rare -- a value is appended only if it is a running maximum of the order the atomics took, about
 // ln(waves) + ln(iterations) per launch -- so this costs no instruction per nonce.
+//
+// A claimed best entry (kEntryClaim too: a background best job, npow_submit_best_background) comes here unchanged.
+// `hits` is taken under the lane mask of the chunk's row as of any row (last_b and tail are the span's, and a chunk's
+// blocks are the span's own), so a lane past the ragged tail is never picked; and the watch lives in the cursor, which
+// is loaded once per entry, outside the per-chunk loop: what a wave learnt in one chunk it still knows in the next.
+// A launch cut short has covered a prefix of chunks, each hashed to its end, and its records hold that prefix's
+// maximum: the argument above, over the prefix.
 __device__ __forceinline__ uint64_t ls2_best(PoolHits* ph, uint32_t slot, uint32_t region, uint32_t room, uint64_t hits,
                                              uint64_t value, uint64_t nonce, uint32_t lane) {
   const int first = __builtin_ctzll(hits);
@@ -1053,8 +1060,8 @@ __device__ __forceinline__ uint64_t ls2_best(PoolHits* ph, uint32_t slot, uint32
   return bv > old ? bv : old;
 }
 
-// A claimed collecting entry (kEntryClaim: a background sweep job, npow_submit_sweep_background; pool_body_ls2, BOUNDED
-// only).  Lane 0 of wave 0, before each chunk: the next chunk index of the entry's span from the launch's claim counter
+// A claimed collecting entry (kEntryClaim: a background sweep job or a background best job,
+// npow_submit_sweep_background, npow_submit_best_background; pool_body_ls2, BOUNDED only).  Lane 0 of wave 0, before each chunk: the next chunk index of the entry's span from the launch's claim counter
 // of the slot (PoolHits::claim, zeroed in stream order with the hit counters: a count belongs to one launch of one
 // generation), or kNoEntry when the workgroup must claim no more -- a stop request is filed (the entry is dead or was
 // killed: the per-iteration path), the entry is dead, the launch's time budget has passed, the host has raised a yield
@@ -1151,7 +1158,8 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
     uint32_t done = 0;
     for (;;) {  // (a claimed entry: once per chunk; every other entry: once)
     if constexpr (BOUNDED) {
-      // Background sweep jobs (kEntryClaim): the entry's own workgroups do not walk the dense mapping; each takes
+      // Background sweep and best jobs (kEntryClaim): the entry's own workgroups do not walk the dense mapping; each
+      // takes
       // chunks of kClaimRows rows of the span from the launch's claim counter (ls2_claim) until the span is used up
       // or the launch must end.  Wave 0 claims and broadcasts the index through LDS (two barriers: every wave has
       // read it before the next claim writes it, as npow_sweep_kernel_ls2's row claims).  Within a chunk `it` is the

@@ -28,12 +28,13 @@
 //
 // The worker's side of the collecting kinds of job (Job::kind; npow_pool_jobs.cpp has the callers' side): a sweep
 // job's entries collect every hit of their ranges in the launch's hit records (PoolHits), which the worker reads as
-// each launch retires (collect_hits, collect_sweep).  A background sweep job (Job::claimed()) is left out of a
-// device's tables while a foreground job is live there (hold_out); its entries are claimed ones (kEntryClaim): a
-// launch covers a prefix of its span, told by its claim counter, and ends at the time budget or a yield;
-// collect_sweep credits the prefix and hands the rest back.  A best job's entries (kEntryBest) keep only the nonces
+// each launch retires (collect_hits, collect_sweep).  A best job's entries (kEntryBest) keep only the nonces
 // that beat the best value their launch has seen: collect_best recomputes each record's value on the CPU and folds it
-// into the job's best (npow_best.h), which the next entry carries as its watch.
+// into the job's best (npow_best.h), which the next entry carries as its watch.  A background job of either kind
+// (Job::claimed()) is left out of a device's tables while a foreground job is live there (hold_out); its entries are
+// claimed ones (kEntryClaim, beside kEntryBest for a best job): a launch covers a prefix of its span, told by its
+// claim counter, and ends at the time budget or a yield; credit_entry, which both collectors call, credits the
+// prefix and hands the rest back.
 //
 // Threads: one persistent worker per device (started by npow_init) owns the device's
 // stream, its slot table and up to two launches in flight (the second is queued only near
@@ -366,10 +367,10 @@ struct Adoption {
   bool readback = false;   // done-shard read-back queued (ev_done[slot] marks it)
   bool no_readback = false;  // finished early and not sampled for verification: freed once inflight is empty
   bool fresh = false;      // adopted since the last launch was built
-  bool held = false;       // a background sweep job's slot left out of the tables: a foreground job wants the device
+  bool held = false;       // a claimed job's slot left out of the tables: a foreground job wants the device
                            // (hold_out); it keeps its generation and its place in the range
-  uint64_t claimed = 0;    // a background sweep job: the nonces its retired launches' claims covered in this generation
-                           // (collect_hits), checked against the slot's done counts when it retires
+  uint64_t claimed = 0;    // a claimed job: the nonces its retired launches' claims covered in this generation
+                           // (credit_entry), checked against the slot's done counts when it retires
   bool new_job = false;    // adopted for the first time on this device (not a re-adoption)
   bool fin_seen = false;   // the kernel published this generation's final count (PoolMailbox::fin) ...
   bool early = false;      // ... and the job was finished from it before retiring
@@ -403,7 +404,7 @@ struct PoolInflight {
   bool bounded;         // its table holds a bounded entry: no entry of the launch carries the background flag
   // Its collecting entries (sweep jobs): the slot and generation of each, and its region of the launch's hit records
   // (PoolHits; the set is ring & 1), `room` records from record region * room on.  Read when the launch retires.
-  // A claimed entry (a background sweep job's, kEntryClaim) also has its span: the launch's claim counter of the slot
+  // A claimed entry (a background sweep or best job's, kEntryClaim) also has its span: the launch's claim counter of the slot
   // tells which prefix of it was covered (npow_claims.h).
   struct Collect {
     int slot;
@@ -566,7 +567,8 @@ class Worker {
   int launch(bool empty_linger = false);
   int queue_readbacks();
   int collect_hits(const PoolInflight& f);
-  void collect_best(Slot& sl, const PoolInflight::Collect& c, uint64_t n, uint64_t stored);
+  void collect_best(Slot& sl, const PoolInflight::Collect& c, const PoolInflight& f, uint64_t n, uint64_t stored);
+  void credit_entry(Slot& sl, const PoolInflight::Collect& c, const PoolInflight& f);
   void collect_sweep(Slot& sl, const PoolInflight::Collect& c, const PoolInflight& f, uint64_t n, uint64_t stored);
   int retire_launches();
   int retire_slots();
@@ -681,7 +683,8 @@ bool Worker::dyn_add(int s) {
   const PoolShape sh = pool_shape(d_);
   const PoolInflight& f = q_.back();
   if (!f.counted) return false;  // a one-entry launch: the new job ends it (a yield) instead
-  // a launch of background sweep jobs: its workgroups stay on their claimed entries until the spans are used up, so a
+  // a launch of claimed jobs (background sweep / best): its workgroups stay on their claimed entries until the spans
+  // are used up, so a
   // foreground job that joined would wait for that; it ends the launch instead (a yield: within one chunk)
   if (f.claimed() && !j.background) return false;
   if ((uint32_t)((uint32_t)ctl_ - (uint32_t)f.dyn_base) >= (uint32_t)kDynEntries) return false;
@@ -727,7 +730,7 @@ void Worker::yield_if_long() {
   int live = 0;
   for (const Slot& sl : slots_)
     if (sl.state == SlotState::kActive && !sl.fresh && !sl.job->max_per_dev) ++live;
-  // (a launch of background sweep jobs is ended whatever it holds: nothing foreground is in it -- hold_out -- and the
+  // (a launch of claimed jobs is ended whatever it holds: nothing foreground is in it -- hold_out -- and the
   // job that waits cannot join it)
   bool claimed = false;
   for (const PoolInflight& f : q_) claimed = claimed || f.claimed();
@@ -735,7 +738,8 @@ void Worker::yield_if_long() {
   bool any = false;
   for (int s = 0; s < kMaxSlots; ++s) {
     Slot& sl = slots_[s];
-    // a background sweep job in the running launch: the yield ends its claims; the slot stays as it is, and what the
+    // a claimed job (background sweep / best) in the running launch: the yield ends its claims; the slot stays as it
+    // is, and what the
     // launch did not reach goes back to the job when the launch retires (collect_hits)
     // (held from now on, as hold_out holds it: the next table is queued behind the ending launch at once -- live_slot)
     if (sl.state == SlotState::kActive && !sl.inflight.empty() && sl.job->claimed()) {
@@ -969,7 +973,7 @@ void Worker::check_slots() {
       stop_slot(s, true);  // in-flight waves stop
       sl.stop_us = now_us();
     } else if (sl.no_more && !(j.claimed() && !sl.inflight.empty())) {
-      // (a background sweep job's launches may hand part of their spans back: its slot stays until they have retired)
+      // (a claimed job's launches may hand part of their spans back: its slot stays until they have retired)
       if (sl.held) {  // (held at a yield, and the launches covered all that was left)
         std::lock_guard<std::mutex> g(g_pool.mu);
         JobDev& jd = j.dev[sl.k];
@@ -1099,10 +1103,11 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
   }
 }
 
-// Background sweep jobs among the slots idx[] of the next table: while a foreground job is live on this device -- in a
-// launch in flight, or among idx[] itself, waiting for this table -- their slots are left out of it (and of live_slot():
-// nothing waits for them).  They keep their generation and their queue of ranges; the time they sit out is the job's
-// held_us (npow_ticket_sweep).  Returns the new n.
+// Claimed jobs (background sweep jobs, background best jobs) among the slots idx[] of the next table: while a
+// foreground job is live on this device -- in a launch in flight, or among idx[] itself, waiting for this table --
+// their slots are left out of it (and of live_slot(): nothing waits for them).  They keep their generation and their
+// queue of ranges; the time they sit out is the job's held_us (npow_ticket_sweep, npow_ticket_best_hold).  Returns
+// the new n.
 uint32_t Worker::hold_out(int* idx, uint32_t n) {
   std::lock_guard<std::mutex> g(g_pool.mu);  // Job::background of the searches (pool_promote), JobDev
   bool fg = foreground_live(-1);
@@ -1273,7 +1278,7 @@ int Worker::collect_hits(const PoolInflight& f) {
                             hipMemcpyDeviceToHost, d_.hit_stream));
       HIPTRY(hipStreamSynchronize(d_.hit_stream));
     }
-    if (sl.job->is_best()) collect_best(sl, c, n, stored);
+    if (sl.job->is_best()) collect_best(sl, c, f, n, stored);
     else collect_sweep(sl, c, f, n, stored);
   }
   return NPOW_OK;
@@ -1284,7 +1289,8 @@ int Worker::collect_hits(const PoolInflight& f) {
 // CPU, and nothing else of the record is trusted; a nonce outside the entry's span, or more records than the region
 // holds (n > stored: the maximum may be among the lost ones), fails the job -- it never returns a possibly wrong
 // answer.
-void Worker::collect_best(Slot& sl, const PoolInflight::Collect& c, uint64_t n, uint64_t stored) {
+void Worker::collect_best(Slot& sl, const PoolInflight::Collect& c, const PoolInflight& f, uint64_t n,
+                          uint64_t stored) {
   Job& j = *sl.job;
   std::vector<uint64_t> values(stored);
   bool outside = false;
@@ -1308,9 +1314,33 @@ void Worker::collect_best(Slot& sl, const PoolInflight::Collect& c, uint64_t n, 
     notify_workers_locked();
     return;
   }
+  // (the records of a launch that was cut are folded like any: the next table's entry carries best_watch of them)
   const uint64_t floor = j.threshold.load(std::memory_order_relaxed);
   for (uint64_t i = 0; i < stored && !outside; ++i) best_fold(j.best.of, j.start, floor, d_.h_hits[i], values[i]);
-  if (sl.stop_us == 0 && !j.decided.load()) jd.progress += c.count;
+  credit_entry(sl, c, f);
+}
+
+// What retired launch f covered of collecting entry c's span is credited to its job (caller holds g_pool.mu): all of
+// it -- or, a claimed entry (a background job's), the first `claims` chunks, claim_prefix(c.count, claims) nonces
+// (npow_claims.h); the rest goes back to the front of the device's queue of ranges, in range order (credit_launch,
+// npow_credit.h), and the slot is offered to the next table.  Nothing is credited once the slot's generation has stopped (a cancel: its launches ended part-way; the
+// done counts' read-back tells what was hashed).  Sweep jobs and best jobs alike.
+void Worker::credit_entry(Slot& sl, const PoolInflight::Collect& c, const PoolInflight& f) {
+  Job& j = *sl.job;
+  JobDev& jd = j.dev[sl.k];
+  if (sl.stop_us > 0 || j.decided.load()) return;
+  const LaunchCredit cr =
+      credit_launch(jd.todo, j.start, c.base, c.count, c.claim, c.claim ? d_.h_hit_n[kMaxSlots + c.slot] : 0);
+  if (c.claim) {
+    sl.claimed += cr.covered;
+    for (Slot::Issued& r : sl.inflight)
+      if (r.seq == f.seq && r.base == c.base) r.count = cr.covered;
+    if (cr.cut) {
+      jd.launches_cut++;
+      sl.no_more = false;
+    }
+  }
+  jd.progress += cr.covered;
 }
 
 // A sweep job's entry c of retired launch f, its `stored` records in d_.h_hits (collect_hits): the hits go to the
@@ -1325,28 +1355,8 @@ void Worker::collect_sweep(Slot& sl, const PoolInflight::Collect& c, const PoolI
   if (n > stored) jd.hits_lost = true;
   const uint64_t take = std::min<uint64_t>(stored, (uint64_t)NPOW_SWEEP_JOB_HITS - jd.hits.size());
   jd.hits.insert(jd.hits.end(), d_.h_hits, d_.h_hits + take);
-  // What the launch covered of the entry's span: all of it -- or, a claimed entry, the first `claims` chunks
-  // (npow_claims.h); the rest goes back to the front of the device's queue of ranges (kept in range order: with
-  // two launches in flight the later one's span lies after this one's), and the slot is offered to the next table.
-  // Nothing is credited once the slot's generation has stopped (a cancel: its launches ended part-way; the done
-  // counts' read-back tells what was hashed).
   jd.launches++;
-  if (sl.stop_us > 0 || sl.job->decided.load()) return;
-  uint64_t covered = c.count;
-  if (c.claim) {
-    covered = claim_prefix(c.count, d_.h_hit_n[kMaxSlots + c.slot]);
-    sl.claimed += covered;
-    for (Slot::Issued& r : sl.inflight)
-      if (r.seq == f.seq && r.base == c.base) r.count = covered;
-    if (covered < c.count) {
-      jd.launches_cut++;
-      jd.todo.push_front({c.base + covered, c.count - covered});
-      std::sort(jd.todo.begin(), jd.todo.end(),
-                [start](const Range& x, const Range& y) { return x.base - start < y.base - start; });
-      sl.no_more = false;
-    }
-  }
-  jd.progress += covered;
+  credit_entry(sl, c, f);
 }
 
 // The launches that have completed, in order: their statistics, and the ranges they held leave the slots' inflight.
@@ -1464,8 +1474,9 @@ int Worker::retire_slots() {
       Job& j = *sl.job;
       credit_job_locked(sl, c);
       if (j.claimed() && !j.decided && !d_.dead && c.done != sl.claimed) {
-        // a background sweep job: the nonces its workgroups counted are not the prefixes its launches' claims covered
-        j.err = "background sweep job: device " + std::to_string(d_.id) + " hashed " + std::to_string(c.done) +
+        // a claimed job: the nonces its workgroups counted are not the prefixes its launches' claims covered
+        j.err = std::string(j.is_best() ? "background best job" : "background sweep job") + ": device " +
+                std::to_string(d_.id) + " hashed " + std::to_string(c.done) +
                 " nonces where its claims cover " + std::to_string(sl.claimed);
         decide_locked(j, NPOW_ERR_INTERNAL);
         g_pool.decisions.fetch_add(1, std::memory_order_release);

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "npow_best.h"
+#include "npow_credit.h"
 #include "npow_host.h"
 
 namespace npow {
@@ -23,10 +24,7 @@ inline double now_us() {       // steady clock, microseconds
   return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// [base, base + count) mod 2^64: nonces of a job still to be handed to launches
-struct Range {
-  uint64_t base, count;
-};
+// (Range -- [base, base + count) mod 2^64, nonces of a job still to be handed to launches -- is npow_credit.h's)
 
 // A job's state on the k-th of its devices (Job::dev[k]; guarded by g_pool.mu)
 struct JobDev {
@@ -49,7 +47,8 @@ struct JobDev {
   std::vector<uint64_t> hits;
   uint64_t hit_n = 0;
   bool hits_lost = false;
-  // What npow_ticket_sweep reports of a sweep job on this device (Worker::collect_hits, Worker::hold_out).
+  // What npow_ticket_sweep, npow_ticket_best and npow_ticket_best_hold report of a collecting job on this device
+  // (Worker::credit_entry, Worker::hold_out).
   // progress: the nonces the retired launches covered (a launch's whole span; of a background job's launch the prefix
   // its claims covered, npow_claims.h).  launches_cut: launches of a background job that ended with part of their span
   // unhashed (a yield, the time budget).  held_us / held_since: how long the job's slot was left out of this device's
@@ -81,18 +80,19 @@ struct Job {
   // A sweep job (npow_submit_sweep): a bounded job (max_per_dev != 0: its devices' largest part) that never wins --
   // its entries collect every hit of [start, start + count) (PoolEntry::bounded kEntryCollect, JobDev::hits), each
   // device a contiguous part.  Only pool_wait_sweep collects its ticket; a part is never handed to another device.
-  // With `background` set (npow_submit_sweep_background; it never changes: npow_promote refuses the ticket) its entries
-  // are claimed ones (kEntryClaim) and a device leaves its slot out of every table built while a foreground job is live
-  // there (Worker::hold_out).
-  // A best job (npow_submit_best; `background` never): a sweep job's sibling whose entries keep only what beats the
+  // A best job (npow_submit_best): a sweep job's sibling whose entries keep only what beats the
   // best value so far (PoolEntry::bounded kEntryBest).  Same admission, parts, range queues and retirement; its
   // launches' few records are validated on the CPU and folded into `best.of` as they retire (Worker::collect_best,
   // npow_best.h), and each new entry carries best_watch() as its threshold.  `threshold` holds the floor.  Only
   // pool_wait_best collects its ticket.
+  // Either collecting kind with `background` set (npow_submit_sweep_background, npow_submit_best_background; it never
+  // changes: npow_promote refuses the ticket) is a claimed job: its entries are claimed ones (kEntryClaim, beside
+  // kEntryBest for a best job) and a device leaves its slot out of every table built while a foreground job is live
+  // there (Worker::hold_out).
   JobKind kind = JobKind::kSearch;
   bool collects() const { return kind != JobKind::kSearch; }  // its entries collect records: a sweep or a best job
   bool is_best() const { return kind == JobKind::kBest; }
-  bool claimed() const { return kind == JobKind::kSweep && background; }
+  bool claimed() const { return collects() && background; }  // a collecting job of the background class
   struct Best {  // a best job's own state (guarded by g_pool.mu)
     BestFold of;
     uint64_t records = 0;      // records read from its retired launches, and ...

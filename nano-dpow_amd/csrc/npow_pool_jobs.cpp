@@ -12,9 +12,10 @@
 // pool_wait_sweep merges them.  DESIGN.md section 1 "Sweep jobs".  With Job::background
 // (npow_submit_sweep_background) the workers leave it out of a device's tables while a foreground job is live there.
 // DESIGN.md section 1 "Background sweep jobs".
-// A best job (npow_submit_best) is a foreground sweep job whose entries (kEntryBest) keep only the nonces that beat
+// A best job (npow_submit_best) is a sweep job whose entries (kEntryBest) keep only the nonces that beat
 // the best value their launch has seen; the workers fold them into the job's best (Worker::collect_best), and
-// pool_wait_best returns it.  DESIGN.md section 1 "Best jobs".
+// pool_wait_best returns it.  DESIGN.md section 1 "Best jobs".  With Job::background (npow_submit_best_background) it
+// is of the background sweep job's class, claimed entries and all.  DESIGN.md section 1 "Background best jobs".
 #include <algorithm>
 
 #include "npow_pool_impl.h"
@@ -479,7 +480,8 @@ static int submit_collecting(const uint8_t root[32], uint64_t threshold, uint64_
                              bool background) {
   auto j = std::make_shared<Job>();
   j->kind = kind;  // (a best job: `threshold` is its floor)
-  j->background = background;  // (npow_submit_sweep_background: admitted as a background search is, admit_locked)
+  j->background = background;  // (npow_submit_sweep_background, npow_submit_best_background: admitted as a background
+                               // search is, admit_locked)
   j->count = count;
   j->pre = host_precompute(root);
   npow_asm_uniforms(j->pre.m, j->u);
@@ -583,10 +585,11 @@ int pool_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t
 // The strongest nonce of [start, start + count): a sweep job's sibling (submit_collecting with kBest: the same split,
 // admission and queue) whose entries keep only what beats the best so far (kEntryBest).  The workers fold each retired
 // launch's records into Job::best.of (Worker::collect_best); this only reads the result.  DESIGN.md section 1 "Best
-// jobs".
+// jobs".  background (npow_submit_best_background): the class of a background sweep job -- claimed entries, held out
+// while a foreground job wants the device (Job::claimed()).
 int pool_submit_best(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count, uint64_t device_mask,
-                     const volatile uint32_t* cancel, uint64_t* ticket) {
-  return submit_collecting(root, floor, start, count, device_mask, cancel, ticket, JobKind::kBest, false);
+                     const volatile uint32_t* cancel, uint64_t* ticket, bool background) {
+  return submit_collecting(root, floor, start, count, device_mask, cancel, ticket, JobKind::kBest, background);
 }
 
 int pool_ticket_best(uint64_t ticket, npow_best_info* out) {
@@ -609,6 +612,25 @@ int pool_ticket_best(uint64_t ticket, npow_best_info* out) {
   out->records_max = j.best.records_max;
   out->room = j.best.room;
   out->finished = fin ? 1u : 0u;
+  return NPOW_OK;
+}
+
+// A best job's class and what it cost it (npow_ticket_best_hold), read as pool_ticket_sweep reads a sweep job's; a
+// plain best job is never cut or held: zeros.
+int pool_ticket_best_hold(uint64_t ticket, npow_best_hold_info* out) {
+  std::lock_guard<std::mutex> g(g_pool.mu);
+  const JobP jp = ticket_job_locked(ticket);
+  if (!jp) return NPOW_ERR_BAD_ARGUMENT;
+  const Job& j = *jp;
+  if (int rc = expect_kind(j, JobKind::kBest, "npow_ticket_best_hold")) return rc;
+  const double t = j.finished.load() ? j.t_finish : now_us();
+  double held = 0;
+  for (const JobDev& jd : j.dev) {
+    out->launches_cut += jd.launches_cut;
+    held += jd.held_us + (jd.held_since > 0 && t > jd.held_since ? t - jd.held_since : 0.0);
+  }
+  out->background = j.background ? 1u : 0u;
+  out->held_us = (uint64_t)held;
   return NPOW_OK;
 }
 

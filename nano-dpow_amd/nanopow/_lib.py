@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "npow_promote", "npow_retarget", "npow_submit_background", "npow_ticket_background",
     "npow_submit_reserve", "npow_ticket_reserve", "npow_relax", "npow_submit_sweep", "npow_wait_sweep",
     "npow_submit_sweep_background", "npow_ticket_sweep", "npow_submit_best", "npow_wait_best", "npow_ticket_best",
+    "npow_submit_best_background", "npow_ticket_best_hold",
 )
 
 
@@ -202,6 +203,27 @@ class BestInfo:
     room: int              # the fewest records one of its entries had room for (0: no launch retired yet)
 
 
+class _BestHoldStruct(ctypes.Structure):
+    """npow_best_hold_info as the C ABI lays it out (npow_ticket_best_hold)."""
+    _fields_ = [
+        ("size", ctypes.c_uint32),
+        ("background", ctypes.c_uint32),
+        ("launches_cut", ctypes.c_uint64),
+        ("held_us", ctypes.c_uint64),
+    ]
+
+
+@dataclass
+class BestHold:
+    """A best job's class and what it cost it (BestTicket.hold, npow_ticket_best_hold); a plain job reads 0, 0, 0."""
+    background: int        # 1: submitted with background=True
+    launches_cut: int      # launches a yield or the time budget ended before their span was hashed
+    held_us: int           # time the job sat admitted but left out of its devices' tables
+
+    def __iter__(self):    # background, launches_cut, held_us = ticket.hold()
+        return iter((self.background, self.launches_cut, self.held_us))
+
+
 @dataclass
 class BestResult:
     status: int            # NPOW_OK / NPOW_EXHAUSTED (nothing reached the floor) / NPOW_CANCELLED
@@ -340,6 +362,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.npow_wait_best.restype = ctypes.c_int
             lib.npow_ticket_best.argtypes = [u64, ctypes.POINTER(_BestInfoStruct)]
             lib.npow_ticket_best.restype = ctypes.c_int
+        if hasattr(lib, "npow_submit_best_background"):  # added within ABI 7: probed for
+            lib.npow_submit_best_background.argtypes = [u8p, u64, u64, u64, u64, p, pu64]
+            lib.npow_submit_best_background.restype = ctypes.c_int
+            lib.npow_ticket_best_hold.argtypes = [u64, ctypes.POINTER(_BestHoldStruct)]
+            lib.npow_ticket_best_hold.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -645,6 +672,19 @@ class BestTicket(_JobTicket):
         return BestInfo(bool(i.finished), i.count, i.nonces_done, i.nonce, i.value, i.launches, i.records,
                         i.records_max, i.room)
 
+    def hold(self) -> BestHold:
+        """The job's class, the launches cut and the time held out (npow_ticket_best_hold); never waits for a GPU.
+        NanoPowError(NPOW_ERR_BAD_ARGUMENT) once the ticket is collected, or when the loaded library has no
+        npow_ticket_best_hold."""
+        lib = self.engine.lib
+        self._need(lib, "npow_ticket_best_hold")
+        if not self.ticket:
+            raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the best ticket is collected")
+        i = _BestHoldStruct()
+        i.size = ctypes.sizeof(_BestHoldStruct)
+        _check(lib.npow_ticket_best_hold(self.ticket, ctypes.byref(i)), lib)
+        return BestHold(i.background, i.launches_cut, i.held_us)
+
     def _collect_abandoned(self, lib) -> int:
         n, v = ctypes.c_uint64(0), ctypes.c_uint64(0)
         return lib.npow_wait_best(self.ticket, 10_000_000, ctypes.byref(n), ctypes.byref(v), None)
@@ -804,16 +844,20 @@ class Engine:
         return SweepTicket(self, t.value, cancel, cap)
 
     def submit_best(self, root: bytes, start: int, count: int, floor: int = 0, device_mask: int = 0,
-                    cancel: Optional[CancelToken] = None) -> BestTicket:
+                    cancel: Optional[CancelToken] = None, background: bool = False) -> BestTicket:
         """Queue a best job and return at once (npow_submit_best): the nonce of [start, start + count) with the
         highest work value, found inside the work pool's launches beside the live searches -- exact at any floor
         (only values >= floor are candidates; 0 allowed).  BestTicket.wait gives status, nonce, value, nonces_done.
-        Keep `cancel` alive until then (the ticket holds a reference).  NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the
-        loaded library lacks the call."""
-        _JobTicket._need(self.lib, "npow_submit_best")
+        Keep `cancel` alive until then (the ticket holds a reference).
+        background=True (npow_submit_best_background): each GPU hashes the job only while no foreground job wants
+        it, and a search that arrives waits one short chunk; the best so far (BestTicket.info) survives every
+        interruption; continuous foreground load starves the job.  BestTicket.hold tells what the class cost.
+        NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the loaded library lacks the call."""
+        name = "npow_submit_best_background" if background else "npow_submit_best"
+        _JobTicket._need(self.lib, name)
         t = ctypes.c_uint64(0)
-        _check(self.lib.npow_submit_best(_root(root), floor & M64, start & M64, count, device_mask,
-                                         cancel.address if cancel else None, ctypes.byref(t)), self.lib)
+        _check(getattr(self.lib, name)(_root(root), floor & M64, start & M64, count, device_mask,
+                                       cancel.address if cancel else None, ctypes.byref(t)), self.lib)
         return BestTicket(self, t.value, cancel)
 
     def sweep(self, root: bytes, threshold: int, start: int, count: int, device_mask: int = 0,

@@ -57,7 +57,11 @@ it, in place (npow_relax: decided at once from its reserve when that qualifies).
 ``"start"``, 16 hex digits, and ``"difficulty"``, a floor) hashes exactly N nonces (at most
 2^40) and answers with the strongest: ``{"work", "difficulty", "multiplier", "hashes"}``
 (npow_submit_best), ``{"error": "Exhausted"}`` when nothing reached the floor, and
-``{"error": "Cancelled"}`` after a ``work_cancel`` of the hash.
+``{"error": "Cancelled"}`` after a ``work_cancel`` of the hash.  With ``"background": true``
+(a JSON boolean, as ``work_generate``'s) it is a background best job
+(npow_submit_best_background): the GPUs hash it only while no foreground request wants
+them, so a long one can run beside ``work_generate`` traffic -- and makes no progress
+while that traffic is continuous.  The reply is the same.
 The reference serves one request at a time; here up to ``max_active`` queued
 requests are handed to libnanopow's work pool at once (npow_submit), where
 every selected GPU searches all of them in the same kernel launches, so a
@@ -408,10 +412,13 @@ class WorkServer:
         job, npow_submit_best): best-effort work at a cost fixed in advance.  ``"start"`` (16 hex digits; random
         when absent) is the range's first nonce and ``"difficulty"`` a floor below which nothing is returned
         (``{"error": "Exhausted"}``).  The job queues in the engine like a bounded search; it is not shared with
-        other requests, and a work_cancel of the hash cancels it."""
+        other requests, and a work_cancel of the hash cancels it.  ``"background": true`` (a JSON boolean) makes it a
+        background best job (npow_submit_best_background): hashed only while no foreground job wants the GPUs.  The
+        keyword is passed to the engine only when it is set, as work_generate's is."""
         root = W.parse_hash(req)
         count = W.parse_best_count(req)
         start = W.parse_start(req)
+        background = W.parse_background(req)
         floor = W.parse_threshold(req["difficulty"]) if req.get("difficulty") is not None else 0
         if start is None:
             start = self.rng.getrandbits(64)
@@ -423,8 +430,9 @@ class WorkServer:
             self._best.append(entry)
         try:
             t0 = time.perf_counter()
+            extra = {"background": True} if background else {}
             ticket = self.engine.submit_best(root, start, count, floor=floor, device_mask=self.device_mask,
-                                             cancel=cancel)
+                                             cancel=cancel, **extra)
             status, nonce, value, done = ticket.wait()
             if status == NPOW_CANCELLED:
                 return {"error": "Cancelled"}

@@ -137,8 +137,9 @@ WEIGHTS = (1, 2, 4, 8)
 
 
 def parse_background(req: Dict[str, Any]) -> bool:
-    """The optional ``"background"`` of a work_generate request (a JSON boolean; this server's extension): the
-    search hashes only on what no foreground search wants (npow_submit_background).  False when absent."""
+    """The optional ``"background"`` of a work_generate or work_best request (a JSON boolean; this server's
+    extension): the search hashes only on what no foreground search wants (npow_submit_background), the best job only
+    while no foreground job wants the GPU (npow_submit_best_background).  False when absent."""
     b = req.get("background")
     if b is None:
         return False
