@@ -561,6 +561,48 @@ typedef struct npow_best_hold_info {
  * waits for a GPU. */
 int npow_ticket_best_hold(uint64_t ticket, npow_best_hold_info* out);
 
+/* Shared range jobs (added within ABI 7; probe for the symbols): a sweep job or a best job that takes a weighted
+ * share of each GPU beside the searches -- the class between the plain one, whose launches no search can join or cut
+ * short, and the background one, which continuous foreground load starves.  A shared job always makes progress, and a
+ * search that arrives waits about one chunk of 8,192 nonces per workgroup (~0.3 ms), not a launch.
+ *
+ * The arguments, the split of the range over the GPUs of device_mask, the statuses and the guarantees are exactly
+ * those of npow_submit_sweep / npow_submit_best (every nonce hashed exactly once; hits ascending by nonce - start and
+ * *n_out exact, or the maximum of the range with the smallest nonce - start among equal values; a dropped device fails
+ * the job; a cancel returns what was found).  npow_wait_sweep, npow_ticket_sweep, npow_wait_best, npow_ticket_best,
+ * npow_ticket_best_hold and npow_cancel work on the ticket as they do on the plain job's; every other ticket call
+ * returns NPOW_ERR_BAD_ARGUMENT and leaves it collectable.  count == 0 completes at once and touches no device.
+ *
+ * The job is admitted as a plain one is: a foreground job of weight 1 that takes a slot and counts against
+ * npow_pool_config's limit.  Its entries are claimed ones, as the background class's: a launch takes its span in
+ * chunks and gives the device back within one chunk once a search arrives or the launch's time budget passes; what it
+ * did not reach goes back to the job.  But it is never held out of a table (held_us stays 0): the next launch holds the
+ * search and the job.  Beside searches it weighs 1 in the launch's start map -- a weight-8 search beside it starts with
+ * 8/9 of the workgroups -- and the workgroups of a search that ends early in a launch move to the job's chunks instead
+ * of leaving the launch (npow_range_share_info.moves).  Background sweep and best jobs share its launches and are not
+ * starved by it.  npow_sweep_info.background and npow_best_hold_info.background read 0 for it: the class is reported
+ * by npow_ticket_share alone. */
+int npow_submit_sweep_shared(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count,
+                             uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket);
+int npow_submit_best_shared(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count,
+                            uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket);
+
+/* The class of an uncollected sweep or best job's ticket and what came with it (npow_ticket_share). */
+typedef struct npow_range_share_info {
+  uint32_t size;          /* set by the caller; written up to it */
+  uint32_t klass;         /* 0 plain, 1 background, 2 shared */
+  uint64_t launches;      /* launches that held an entry of the job, summed over its devices */
+  uint64_t launches_cut;  /* of those, launches that ended with part of their span unhashed (claimed entries only) */
+  uint64_t held_us;       /* time the job sat admitted but left out of its devices' tables (background jobs only) */
+  uint64_t moves;         /* workgroups that came to the job's claimed entry from another entry of a running launch
+                           * (counted in the kernel, read as each launch retires); 0 for plain jobs */
+} npow_range_share_info;
+
+/* Any sweep or best ticket (added within ABI 7; probe for the symbol).  Written up to out->size.
+ * NPOW_ERR_BAD_ARGUMENT for a search's ticket, an unknown or collected one, or out / out->size missing.  Never waits
+ * for a GPU. */
+int npow_ticket_share(uint64_t ticket, npow_range_share_info* out);
+
 /* Work values of `count` consecutive nonces start, start+1, ... for one root,
  * computed by the instruction stream the search and sweep kernels execute
  * (npow_values_kernel_ls2: the same uniform loads, priority runs and

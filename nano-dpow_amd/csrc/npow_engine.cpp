@@ -810,7 +810,14 @@ int npow_submit_sweep_background(const uint8_t root[32], uint64_t threshold, uin
                                  uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket) try {
   if (int rc = check_init()) return rc;
   if (!root || !ticket) return fail(NPOW_ERR_BAD_ARGUMENT, "root and ticket are required");
-  return pool_submit_sweep(root, threshold, start, count, device_mask, cancel, ticket, true);
+  return pool_submit_sweep(root, threshold, start, count, device_mask, cancel, ticket, 1);
+} catch (...) { return guard_exception(); }
+
+int npow_submit_sweep_shared(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count,
+                             uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket) try {
+  if (int rc = check_init()) return rc;
+  if (!root || !ticket) return fail(NPOW_ERR_BAD_ARGUMENT, "root and ticket are required");
+  return pool_submit_sweep(root, threshold, start, count, device_mask, cancel, ticket, 2);
 } catch (...) { return guard_exception(); }
 
 int npow_ticket_sweep(uint64_t ticket, npow_sweep_info* out) try {
@@ -864,7 +871,27 @@ int npow_submit_best_background(const uint8_t root[32], uint64_t floor, uint64_t
                                 uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket) try {
   if (int rc = check_init()) return rc;
   if (!root || !ticket) return fail(NPOW_ERR_BAD_ARGUMENT, "root and ticket are required");
-  return pool_submit_best(root, floor, start, count, device_mask, cancel, ticket, true);
+  return pool_submit_best(root, floor, start, count, device_mask, cancel, ticket, 1);
+} catch (...) { return guard_exception(); }
+
+int npow_submit_best_shared(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count,
+                            uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket) try {
+  if (int rc = check_init()) return rc;
+  if (!root || !ticket) return fail(NPOW_ERR_BAD_ARGUMENT, "root and ticket are required");
+  return pool_submit_best(root, floor, start, count, device_mask, cancel, ticket, 2);
+} catch (...) { return guard_exception(); }
+
+int npow_ticket_share(uint64_t ticket, npow_range_share_info* out) try {
+  if (int rc = check_init()) return rc;
+  if (!out || out->size < offsetof(npow_range_share_info, launches))
+    return fail(NPOW_ERR_BAD_ARGUMENT, "out with out->size set is required");
+  npow_range_share_info full{};
+  const int rc = pool_ticket_share(ticket, &full);
+  if (rc != NPOW_OK) return rc;
+  const uint32_t n = std::min<uint32_t>(out->size, (uint32_t)sizeof(full));
+  full.size = n;
+  memcpy(out, &full, n);
+  return NPOW_OK;
 } catch (...) { return guard_exception(); }
 
 int npow_ticket_best_hold(uint64_t ticket, npow_best_hold_info* out) try {

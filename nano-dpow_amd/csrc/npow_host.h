@@ -61,6 +61,8 @@ struct Device {
   // sweep jobs (Worker::collect_hits): a retired launch's hit counters and one entry's records are copied on a stream
   // of their own (non-blocking: the next launch may be running on `stream`) into these pinned buffers
   hipStream_t hit_stream = nullptr;
+  unsigned long long* h_hit_ring = nullptr;  // each launch ring's copy of its hit set's counters (PoolHits up to rec),
+                                             // written in stream order right behind the launch (Worker::launch)
   unsigned long long* h_hit_n = nullptr;  // PoolHits::n
   uint64_t* h_hits = nullptr;             // kSweepHits records
   std::thread worker;
@@ -222,11 +224,12 @@ int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered);  // npo
 // sweep jobs (npow_submit_sweep, npow_wait_sweep; arguments checked by the caller)
 int pool_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count, uint64_t device_mask,
                       const volatile uint32_t* cancel, uint64_t* ticket,
-                      bool background = false);  // npow_submit_sweep_background
+                      int klass = 0);  // 1: npow_submit_sweep_background, 2: npow_submit_sweep_shared
 // best jobs (npow_submit_best, npow_wait_best, npow_ticket_best; arguments checked by the caller)
 int pool_submit_best(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count, uint64_t device_mask,
                      const volatile uint32_t* cancel, uint64_t* ticket,
-                     bool background = false);  // npow_submit_best_background
+                     int klass = 0);  // 1: npow_submit_best_background, 2: npow_submit_best_shared
+int pool_ticket_share(uint64_t ticket, npow_range_share_info* out);  // npow_ticket_share (out: a full struct, zeroed)
 int pool_ticket_best(uint64_t ticket, npow_best_info* out);  // (out: a full struct, zeroed)
 int pool_ticket_best_hold(uint64_t ticket, npow_best_hold_info* out);  // npow_ticket_best_hold (out: the same)
 int pool_wait_best(uint64_t ticket, int64_t timeout_us, uint64_t* nonce, uint64_t* value, uint64_t* nonces_done);

@@ -185,9 +185,13 @@ struct PoolTable {
                           // toward every live unbounded entry, not only the dynamic ones
   uint32_t wdown;         // how many times the table's weights were halved (pool_table_weights): a promoted weight,
                           // published raw, is halved alike
-  uint32_t pad;
+  uint32_t pad;           // bit 0 (kTabNoMoves, test hooks only): no workgroup moves to a claimed entry (ls2_move_claimed)
+                          // bits 1..10 and 16..31: the claimed map's modulus and multiplier (pool_claimed_pad,
+                          // npow_weights.h) of a table whose bounded entries are all claimed, 0: none -- the bounded
+                          // kernels deal its start themselves (ls2_claimed_start), wsum is 0
   PoolEntry e[kMaxSlots];
 };
+constexpr uint32_t kTabNoMoves = 1u;
 inline size_t pool_table_bytes(uint32_t n) { return offsetof(PoolTable, e) + (size_t)n * sizeof(PoolEntry); }
 
 // The same table with at most kArgEntries entries, passed by value as the launch's kernel
@@ -256,6 +260,9 @@ struct PoolHits {
                                         // launch (kEntryBest; zeroed with n and claim, one launch's all three: a
                                         // wave's own watch starts at the entry's threshold, so the word needs no
                                         // seed) -- raised with a device-scope atomic max
+  unsigned long long moves[kMaxSlots];  // workgroups that joined the slot's claimed entry in this launch from another
+                                        // entry of it (ls2_move_claimed: a search of the launch no longer wanted
+                                        // them); zeroed and read with the three above
   uint64_t rec[kSweepHits];        // the nonces, region by region, each in the order its waves came
 };
 struct PoolDevState {

@@ -1081,6 +1081,74 @@ __device__ __forceinline__ uint32_t ls2_claim(const PoolTable* tab, PoolDevState
   return k < (unsigned long long)claim_chunks(ce->count) ? (uint32_t)k : kNoEntry;
 }
 
+// Shared range jobs (npow_submit_sweep_shared, npow_submit_best_shared; pool_body_ls2, BOUNDED only).  Wave 0 (every
+// lane) of a workgroup that left an entry and found no live unbounded entry to move to (ls2_pick: kNoEntry): before it
+// leaves the launch it looks for a claimed entry of the table that still has chunks -- its dead word below its
+// generation, the launch's claim counter of its slot below the span's chunks -- unless the launch's time budget has
+// passed or the host has raised a yield (ls2_claim would refuse the first claim then).  Each lane looks at one table
+// entry (dynamic entries are never bounded); of several it takes the one with the fewest workgroups on it (ls2_wgs),
+// ties broken by ls2_choose's hash of the workgroup index.  Lane 0 joins it as any entry is joined (ls2_join: count,
+// check the dead word, leave again if it is over -- so the last leaver of a dead entry still finds every joiner
+// counted) and adds 1 to the launch's move counter of the slot (PoolHits::moves).  The workgroup then enters the
+// entry's claim loop like one that started there: a claimed entry takes nothing from g or e.  Without this the
+// workgroups of a search won early in a launch idled beside a range job that still had chunks.
+// Not inlined: the hash loop's registers stay as they were (tools/kernel_loop_census.py).
+__device__ __noinline__ uint32_t ls2_move_claimed(const PoolTable* tab, PoolDevState* st, PoolMailbox* mb,
+                                                  uint32_t t_start) {
+  const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), g = blockIdx.x;
+  if (tab->pad & kTabNoMoves) return kNoEntry;
+  if (tab->budget && (uint32_t)__builtin_amdgcn_s_memrealtime() - t_start >= tab->budget) return kNoEntry;
+  if ((ls2_ctl(mb) >> 32) != (tab->yield_base >> 32)) return kNoEntry;
+  PoolHits* ph = &st->hits[tab->ring & 1u];
+  const uint32_t n = tab->n < (uint32_t)kMaxSlots ? tab->n : (uint32_t)kMaxSlots;
+  for (int attempt = 0; attempt < 4; ++attempt) {
+    unsigned long long key = ~0ull;
+    if (lane < n) {
+      ConstEntry* q = (ConstEntry*)(uintptr_t)&tab->e[lane];
+      const uint32_t slot = q->slot;
+      if ((q->bounded & kEntryClaim) && slot < (uint32_t)kMaxSlots && load_dead(st, slot) < q->gen &&
+          __hip_atomic_load(&ph->claim[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
+              (unsigned long long)claim_chunks(q->count)) {
+        const uint32_t tie = ((lane + 1u) * 0x9e3779b1u) ^ (g * 0x85ebca6bu);
+        key = (ls2_wgs(st, slot) << 32) | (tie & ~63u) | lane;  // (counts are per XCD shard: < 2^27)
+      }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const unsigned long long o = __shfl_xor(key, m);
+      key = o < key ? o : key;
+    }
+    if (key == ~0ull) return kNoEntry;
+    const uint32_t pick = (uint32_t)key & 63u;
+    uint32_t ok = 0;
+    if (lane == 0) {
+      ConstEntry* q = (ConstEntry*)(uintptr_t)&tab->e[pick];
+      ok = ls2_join(st, mb, q->slot, q->gen, true) ? 1u : 0u;  // (only counted launches come here)
+      if (ok) atomicAdd(&ph->moves[q->slot], 1ull);
+    }
+    if (__builtin_amdgcn_readfirstlane(ok)) return pick;
+  }
+  return kNoEntry;  // entries died under every attempt
+}
+
+// Wave 0 (every lane; BOUNDED only): the entry workgroup g of G starts on in a table dealt by the claimed map -- the
+// number of entries whose inclusive prefix sum of the weights 8 >> wsh is at or below pool_claimed_pos, each lane one
+// table entry, as ls2_pick counts them for pool_start_pos.
+__device__ __noinline__ uint32_t ls2_claimed_start(const PoolTable* tab, uint32_t g, uint32_t G, uint32_t csum) {
+  const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  const uint32_t n = tab->n < (uint32_t)kMaxSlots ? tab->n : (uint32_t)kMaxSlots;
+  const uint32_t r = pool_claimed_pos(g, csum, G, pool_claimed_pad_mult(tab->pad));
+  ConstEntry* const le = (ConstEntry*)(uintptr_t)&tab->e[lane < n ? lane : 0u];
+  uint32_t acc = lane < n ? 8u >> (le->wsh & 3u) : 0u;
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    const uint32_t o = __shfl_up(acc, m);
+    if (lane >= (uint32_t)m) acc += o;
+  }
+  const uint32_t k = (uint32_t)__builtin_popcountll(__ballot(lane < n && acc <= r));
+  return k < n ? k : n - 1u;  // (k < n whenever csum is the weights' sum)
+}
+
 // Odd, so that it0 -> -it0 * kPollStride is a bijection modulo every power of two; its residues mod 2^10..2^13 step
 // by 0.43, 0.22, 0.11 and 0.80 of the range (the fractional part of the golden ratio in 32 bits).
 constexpr uint32_t kPollStride = 0x9E3779B9u;
@@ -1113,7 +1181,14 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
     if (n == 0) {
       first = kNoEntry;  // an empty lingering launch (Worker::relaunch_linger): straight to ls2_linger
     } else if (counted) {
-      first = ls2_pick(tab, st, mb, g % n, true, &s_seen);
+      uint32_t e0 = g % n;
+      if constexpr (BOUNDED) {
+        // a table whose bounded entries are all claimed (shared range jobs): the claimed map, exact to a workgroup
+        // (npow_weights.h pool_claimed_pos; PoolTable::pad, wsum is 0: ls2_pick joins the entry it is given)
+        const uint32_t cs = pool_claimed_pad_sum(tab->pad);
+        if (cs) e0 = ls2_claimed_start(tab, g, G, cs);
+      }
+      first = ls2_pick(tab, st, mb, e0, true, &s_seen);
     } else {
       // only the device-side dead word: reading the pinned kill word here too (512 workgroups' PCIe reads
       // at once) delayed every launch's first hash by 30-60 us -- receive-difficulty searches p50 0.29-0.33
@@ -1156,6 +1231,14 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
     uint64_t nonce = c.base + ((uint64_t)b << 6) + lane;
     uint64_t step = (uint64_t)c.K << 6;
     uint32_t done = 0;
+    // (a claimed entry's claims overwrite `it` with rows of its span: the launch's own iteration count, which the cap
+    // below and the workgroup's next unbounded entry go on from, waits in LDS meanwhile -- BOUNDED only; a register
+    // kept across the hash loop for it was spilled to scratch.  Every wave holds the same count; the first claim's
+    // barrier orders the store before the loads after the loop, and the next store comes after the pick's barrier)
+    __shared__ uint32_t s_it;
+    if constexpr (BOUNDED) {
+      if ((c.bounded & kEntryClaim) && wv == 0 && lane == 0) s_it = it;
+    }
     for (;;) {  // (a claimed entry: once per chunk; every other entry: once)
     if constexpr (BOUNDED) {
       // Background sweep and best jobs (kEntryClaim): the entry's own workgroups do not walk the dense mapping; each
@@ -1352,6 +1435,10 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
       late_n = late_n < sum ? late_n : sum;
       ls2_leave_wave(st, mb, c.slot, c.gen, sum, late_n, counted);
     }
+    if constexpr (BOUNDED) {
+      if (c.bounded & kEntryClaim)
+        it = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    }
     if (it >= iters || end || !counted) break;  // an uncounted launch has no other entry
     if (wv == 0) {
       const uint32_t next = ls2_pick(tab, st, mb, e, false, &s_seen);
@@ -1367,7 +1454,21 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
   // no entry to move to (the loop ended on kNoEntry, not on the budget or the iteration cap): a lingering launch's
   // workgroup waits for the host's next one.  (Called here, after the entry loop, and not from ls2_pick: a callee
   // there clobbering more registers made the search loop reload 4 more spilled SGPRs every iteration.)
-  if constexpr (BOUNDED) break;  // (the host sets linger only for launches of unbounded entries)
+  if constexpr (BOUNDED) {
+    // (the host sets linger only for launches of unbounded entries.)  Shared range jobs: the workgroup found no live
+    // unbounded entry to move to -- before it leaves the launch, a claimed entry of the table that still has chunks
+    // takes it (ls2_move_claimed).  Here, after the entry loop, as ls2_linger below and for its reason.
+    if (e != kNoEntry || !counted) break;
+    __syncthreads();  // every wave has read s_next before wave 0 writes it again
+    if (wv == 0) {
+      const uint32_t next = ls2_move_claimed(tab, st, mb, (uint32_t)t_start);
+      if (lane == 0) s_next = next;
+    }
+    __syncthreads();
+    e = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    if (e == kNoEntry) break;
+    continue;
+  }
   if (e != kNoEntry || !tab->linger) break;
   __syncthreads();  // every wave has read s_next before wave 0 writes it again
   if (wv == 0) {

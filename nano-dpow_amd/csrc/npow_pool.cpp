@@ -34,7 +34,9 @@
 // (Job::claimed()) is left out of a device's tables while a foreground job is live there (hold_out); its entries are
 // claimed ones (kEntryClaim, beside kEntryBest for a best job): a launch covers a prefix of its span, told by its
 // claim counter, and ends at the time budget or a yield; credit_entry, which both collectors call, credits the
-// prefix and hands the rest back.
+// prefix and hands the rest back.  A shared job of either kind (Job::shared) has claimed entries too, but is a
+// foreground job that no table leaves out: it weighs 1 in the start map of a table whose bounded entries are all
+// claimed (build_table), and the kernel moves the workgroups its launch's searches no longer want to its entry.
 //
 // Threads: one persistent worker per device (started by npow_init) owns the device's
 // stream, its slot table and up to two launches in flight (the second is queued only near
@@ -55,6 +57,8 @@
 // logical devices; NANOPOW_FAULT_HIP=d:n makes device d's launches fail after its n-th;
 // NANOPOW_FAULT_RETARGET_BLIND=1 makes pool_retarget skip the slots' floor records, so a running launch learns of
 // a raise only through the host's refusal of its win (handle_win's stale path).
+// NANOPOW_SHARED_NO_MOVES=1 turns the kernel's move to a claimed entry off (PoolTable::pad kTabNoMoves; A/B runs of
+// shared range jobs).
 // (npow_engine.cpp: NANOPOW_FAULT_INIT=d fails npow_init on d.)
 #include <hip/hip_runtime.h>
 #include <sys/prctl.h>
@@ -126,10 +130,12 @@ const Faults& faults() {
       if (end && *end == ':') x.hip_after = strtoull(end + 1, nullptr, 10);
     }
     if (const char* e = getenv("NANOPOW_FAULT_RETARGET_BLIND")) x.retarget_blind = strcmp(e, "1") == 0;
+    if (const char* e = getenv("NANOPOW_SHARED_NO_MOVES")) x.no_moves = strcmp(e, "1") == 0;
     if (x.invalid_mask || x.hip_dev >= 0)
       fprintf(stderr, "nanopow: TEST HOOKS ACTIVE: corrupt wins of device mask %#llx, fail launches of device %d after %llu\n",
               (unsigned long long)x.invalid_mask, x.hip_dev, (unsigned long long)x.hip_after);
     if (x.retarget_blind) fprintf(stderr, "nanopow: TEST HOOKS ACTIVE: retargets write no floor record\n");
+    if (x.no_moves) fprintf(stderr, "nanopow: TEST HOOKS ACTIVE: no workgroup moves to a claimed entry\n");
     return x;
   }();
   return f;
@@ -369,6 +375,9 @@ struct Adoption {
   bool fresh = false;      // adopted since the last launch was built
   bool held = false;       // a claimed job's slot left out of the tables: a foreground job wants the device
                            // (hold_out); it keeps its generation and its place in the range
+  bool ending = false;     // a shared job's slot whose running launch was yielded (yield_if_long): nothing waits for
+                           // that launch (live_slot), so the next table is queued behind it at once, and the slot is
+                           // in it -- it is never held; cleared by its next entry (take_entry)
   uint64_t claimed = 0;    // a claimed job: the nonces its retired launches' claims covered in this generation
                            // (credit_entry), checked against the slot's done counts when it retires
   bool new_job = false;    // adopted for the first time on this device (not a re-adoption)
@@ -449,6 +458,7 @@ class Worker {
   uint64_t retired_seq_ = 0;  // the last launch retire_launches() has dropped (launches retire in order)
   uint64_t seen_version_ = ~0ull;
   int ring_ = 0;
+  uint32_t mult_grid_ = 0, mult_ = 1;  // pool_claimed_mult of the device's grid (build_table)
   std::chrono::steady_clock::time_point front_start_{};  // host estimate of the running launch's start
   uint64_t ctl_ = 0;  // PoolMailbox::ctl (only this worker writes it): yields << 32 | dynamic entries
   uint64_t wake_seen_ = 0;  // Device::wake_seq as of this worker's last nap
@@ -500,13 +510,22 @@ class Worker {
   }
   bool live_slot(int except = -1) const {  // a slot (other than `except`) some launch in flight is hashing
     for (int s = 0; s < kMaxSlots; ++s)
-      if (s != except && slots_[s].state == SlotState::kActive && !slots_[s].fresh && !slots_[s].held) return true;
+      if (s != except && slots_[s].state == SlotState::kActive && !slots_[s].fresh && !slots_[s].held &&
+          !slots_[s].ending)
+        return true;
     return false;
   }
-  bool foreground_live(int except) const {  // live_slot, of a foreground job (caller holds g_pool.mu: Job::background)
-    for (int s = 0; s < kMaxSlots; ++s)
-      if (s != except && slots_[s].state == SlotState::kActive && !slots_[s].fresh && !slots_[s].job->background)
-        return true;
+  // live_slot, of a foreground job (caller holds g_pool.mu: Job::background).  A shared range job is none here: the
+  // background class shares its tables (hold_out), and a new background job ends its launch as it ends theirs
+  // (a search that a yield handed back for re-adoption -- draining with `requeue`, undecided -- is still live: beside
+  // a shared job, which is none, it would otherwise vanish between its yield and its next slot, and a background job
+  // would slip into the table built in between)
+  bool foreground_live(int except) const {
+    for (int s = 0; s < kMaxSlots; ++s) {
+      const Slot& sl = slots_[s];
+      if (s == except || sl.state == SlotState::kFree || sl.job->background || sl.job->shared) continue;
+      if (sl.state == SlotState::kActive ? !sl.fresh : (sl.requeue && !sl.job->decided.load())) return true;
+    }
     return false;
   }
   double budget_left_us() const {  // of the running launch's time budget, by the host's estimate of its start
@@ -667,6 +686,7 @@ void Worker::take_entry(Slot& sl, PoolEntry& pe, uint64_t want, uint64_t seq, do
   if (jd.t_launch == 0) jd.t_launch = t;
   if (jd.todo.empty()) sl.no_more = true;
   sl.fresh = false;
+  sl.ending = false;
 }
 
 // Publish the job of fresh slot s as a dynamic entry of the running launch (npow_internal.h
@@ -742,10 +762,15 @@ void Worker::yield_if_long() {
     // is, and what the
     // launch did not reach goes back to the job when the launch retires (collect_hits)
     // (held from now on, as hold_out holds it: the next table is queued behind the ending launch at once -- live_slot)
+    // (a shared job is not held: its slot goes into that next table, beside the job that waits -- `ending`)
     if (sl.state == SlotState::kActive && !sl.inflight.empty() && sl.job->claimed()) {
       any = true;
-      if (!sl.held) sl.job->dev[sl.k].held_since = now_us();
-      sl.held = true;
+      if (sl.job->shared) {
+        sl.ending = true;
+      } else {
+        if (!sl.held) sl.job->dev[sl.k].held_since = now_us();
+        sl.held = true;
+      }
     }
     if (sl.state != SlotState::kActive || sl.fresh || sl.job->max_per_dev) continue;
     sl.requeue = true;
@@ -1014,7 +1039,7 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
   const uint32_t iters = sh.launch_iters(g_iters.load());
   uint32_t wdown = 0;
   uint32_t weights[kMaxSlots], wshs[kMaxSlots];
-  uint8_t bgs[kMaxSlots];
+  uint8_t bgs[kMaxSlots], kinds[kMaxSlots];
   t.n = n;
   t.poll_mask = poll_mask();
   t.iters = iters;
@@ -1043,6 +1068,20 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
     for (uint32_t e = 0; e < n; ++e) ncollect += slots_[idx[e]].job->collects() ? 1u : 0u;
     while ((1u << cshift) < ncollect) ++cshift;
     collect_.clear();
+    // A shared range job beside other entries: every claimed entry of the table takes a full launch region, as an
+    // unbounded entry does, capped as below -- its workgroups are its share of the start map and then every workgroup
+    // the launch's searches no longer want (ls2_move_claimed), so they must not run out of chunks before the launch's
+    // time budget; what the launch does not claim goes back to the job (credit_entry).  Unless the table holds a dense
+    // entry: it is dealt g % n then, and the entry's own share (PoolShape::own) is what its workgroups can cover.
+    bool shared = false, dense_any = false;
+    for (uint32_t e = 0; e < n; ++e) {
+      const Slot& sl = slots_[idx[e]];
+      const Job& j = *sl.job;
+      const std::deque<Range>& todo = j.dev[sl.k].todo;
+      shared = shared || (j.collects() && j.shared);
+      dense_any = dense_any || (j.collects() ? !j.claimed() : (j.max_per_dev || todo.empty() || todo.front().count < full));
+    }
+    const bool wide = shared && !dense_any && n >= 2;
     for (uint32_t e = 0; e < n; ++e) {
       Slot& sl = slots_[idx[e]];
       const Job& j = *sl.job;
@@ -1052,13 +1091,14 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
         // (a best job's records are rare whatever its floor: the bounded span, and its best so far as the watch)
         const uint32_t room = kSweepHits >> cshift, region = (uint32_t)collect_.size();
         const uint64_t span = j.is_best() ? ~0ull : collect_span(j.threshold, room);
-        take_entry(sl, t.e[e], std::min(sh.own(e, n, iters), span), seq_, t_issue);
+        take_entry(sl, t.e[e], std::min(wide && j.claimed() ? full : sh.own(e, n, iters), span), seq_, t_issue);
         if (j.is_best()) t.e[e].threshold = t.e[e].reserve = best_watch(j.best.of, j.threshold);
         t.e[e].bounded = pool_collect_flags(region, cshift) | (j.claimed() ? kEntryClaim : 0u) |
                          (j.is_best() ? kEntryBest : 0u);
         t.e[e].wsh = pool_wsh(j.weight);
         weights[e] = j.weight;
         bgs[e] = 0;
+        kinds[e] = j.claimed() ? kTableClaimed : kTableDense;
         *bounded = true;
         collect_.push_back({idx[e], sl.gen, region, room, j.claimed(), t.e[e].base, t.e[e].count});
         continue;
@@ -1072,6 +1112,7 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
       t.e[e].wsh = pool_wsh(j.weight);
       weights[e] = j.weight;
       bgs[e] = j.background ? 1 : 0;
+      kinds[e] = dense ? kTableDense : kTableUnbounded;
       *bounded = *bounded || dense;
     }
   }
@@ -1081,6 +1122,7 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
   // g % n == e): g % n.  Only differing weights need the map, and a workgroup must start on every entry, or that
   // entry would stay without one: pool_table_weights (npow_weights.h) halves a crowded table's weights until so.
   t.wsum = 0;
+  uint32_t claimed_map = 0;
   if (!*bounded) {
     // (background jobs, pool_table_weights_bg: weight 0 in a map beside foreground ones, g % n among themselves.  A
     // table with a bounded entry carries no background flag -- take_entry cleared it: its background jobs run as
@@ -1090,9 +1132,24 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
       t.e[e].wsh = wshs[e] | (bgs[e] ? kWshBg : 0u);
       t.e[e].bg = bgs[e];
     }
+  } else {
+    // (a table whose bounded entries are all claimed -- shared range jobs, the background class -- has a map too,
+    // over its jobs' weights: a claimed entry takes its chunks from a counter and nothing from g % n.  Equal weights,
+    // as in every table of the background class alone, still give g % n, and a table with a dense entry always does:
+    // pool_table_weights_claimed, npow_weights.h.  The background flags stay cleared as above.)
+    // Dealt by the claimed map, which is exact to a workgroup (PoolTable::pad carries its modulus and multiplier, wsum
+    // stays 0: only the bounded kernels deal it).
+    if (mult_grid_ != (uint32_t)sh.grid) {  // (a search over grid / 4 candidates: once per grid)
+      mult_grid_ = (uint32_t)sh.grid;
+      mult_ = pool_claimed_mult(mult_grid_);
+    }
+    const uint32_t mult = mult_;
+    const uint32_t csum = pool_table_weights_claimed(weights, kinds, n, (uint32_t)sh.grid, mult, wshs, &wdown);
+    for (uint32_t e = 0; e < n; ++e) t.e[e].wsh = wshs[e];
+    if (csum) claimed_map = pool_claimed_pad(csum, mult);
   }
   t.wdown = wdown;  // (a promoted weight is published raw: the kernel halves it as the table's were, pool_promoted_wsh)
-  t.pad = 0;
+  t.pad = (faults().no_moves ? kTabNoMoves : 0u) | claimed_map;
   if (lingers(d_) && !*bounded && g_budget_us.load() > 0) {
     // each lingering workgroup reads the pinned ctl word once in P looks (phase g): ~2 reads per look grid-wide
     uint32_t P = 1;
@@ -1110,13 +1167,13 @@ void Worker::build_table(PoolTable& t, const int* idx, uint32_t n, bool* bounded
 // the new n.
 uint32_t Worker::hold_out(int* idx, uint32_t n) {
   std::lock_guard<std::mutex> g(g_pool.mu);  // Job::background of the searches (pool_promote), JobDev
-  bool fg = foreground_live(-1);
-  for (uint32_t e = 0; e < n && !fg; ++e) fg = !slots_[idx[e]].job->background;
+  bool fg = foreground_live(-1);  // (a shared range job is no foreground job here: it never starves the class)
+  for (uint32_t e = 0; e < n && !fg; ++e) fg = !slots_[idx[e]].job->background && !slots_[idx[e]].job->shared;
   const double t = now_us();
   uint32_t m = 0;
   for (uint32_t e = 0; e < n; ++e) {
     Slot& sl = slots_[idx[e]];
-    if (!sl.job->claimed()) {
+    if (!sl.job->held_class()) {  // (a shared job's slot is never held)
       idx[m++] = idx[e];
       continue;
     }
@@ -1150,7 +1207,7 @@ int Worker::launch(bool empty_linger) {
   for (int s = 0; s < kMaxSlots; ++s)
     if (slots_[s].state == SlotState::kActive && !slots_[s].no_more) {
       idx[n++] = s;
-      claimed = claimed || slots_[s].job->claimed();
+      claimed = claimed || slots_[s].job->held_class();
     }
   if (claimed) n = hold_out(idx, n);
   if (n == 0 && !empty_linger) return NPOW_OK;
@@ -1174,7 +1231,7 @@ int Worker::launch(bool empty_linger) {
   // Sweep jobs: this launch's set of hit records (PoolHits) starts from zero counts, in stream order.  Its previous
   // user, the launch before the last, has retired -- at most two are in flight -- and its hits were read then.
   if (!collect_.empty())
-    HIPTRY(hipMemsetAsync(&d_.pst->hits[r & 1], 0, offsetof(PoolHits, rec), d_.stream));  // (n, claim and best)
+    HIPTRY(hipMemsetAsync(&d_.pst->hits[r & 1], 0, offsetof(PoolHits, rec), d_.stream));  // (n, claim, best, moves)
   if (n <= (uint32_t)kArgEntries) {
     HIPTRY(hipEventRecord(d_.ev_start[r], d_.stream));
     HIPTRY(launch_pool_arg(d_.stream, sh.grid, t, bounded, d_.pst, d_.pmb_dev));
@@ -1183,10 +1240,17 @@ int Worker::launch(bool empty_linger) {
     HIPTRY(hipEventRecord(d_.ev_start[r], d_.stream));
     HIPTRY(launch_pool(d_.stream, sh.grid, d_.d_tab[r], bounded, d_.pst, d_.pmb_dev));
   }
+  // The set's counters come back in stream order right behind the launch, into the ring's own pinned copy: they are
+  // there when the stop event fires.  (Copied on the copy stream once the launch had retired, as the records still
+  // are, the worker waited for a copy that ran only when a compute unit had room -- beside a launch whose workgroups
+  // all hash, as a shared job's moves make them, at that launch's end: every early finish and adoption waited with it.)
+  if (!collect_.empty())
+    HIPTRY(hipMemcpyAsync(d_.h_hit_ring + (size_t)r * (offsetof(PoolHits, rec) / sizeof(unsigned long long)),
+                          &d_.pst->hits[r & 1], offsetof(PoolHits, rec), hipMemcpyDeviceToHost, d_.stream));
   HIPTRY(hipEventRecord(d_.ev_stop[r], d_.stream));
   if (q_.empty()) front_start_ = std::chrono::steady_clock::now();
   NPOW_DBGT("nanopow[%d]: launch %llu n=%u linger %u wsum %u (weights halved %u times) yield_base %llx slots:", d_.id,
-            (unsigned long long)seq_, n, t.linger, t.wsum, t.wdown, (unsigned long long)t.yield_base);
+            (unsigned long long)seq_, n, t.linger, t.wsum ? t.wsum : pool_claimed_pad_sum(t.pad), t.wdown, (unsigned long long)t.yield_base);
   for (uint32_t e = 0; e < n; ++e) NPOW_DBG(" %d/g%llu", idx[e], (unsigned long long)t.e[e].gen);
   NPOW_DBG("\n");
   q_.push_back({seq_, r, (uint32_t)ctl_, t.yield_base, t.counted != 0, t.linger != 0, t.wdown, bounded, collect_});
@@ -1264,10 +1328,12 @@ int Worker::collect_hits(const PoolInflight& f) {
   if (f.collect.empty()) return NPOW_OK;
   DEVCHECK(d_, "pool hit read-back");
   PoolHits* set = &d_.pst->hits[f.ring & 1];
-  static_assert(offsetof(PoolHits, claim) == sizeof(PoolHits::n) && offsetof(PoolHits, rec) == 3 * sizeof(PoolHits::n),
-                "the hit and claim counters (and the best words behind them) are read with one copy");
-  HIPTRY(hipMemcpyAsync(d_.h_hit_n, set, offsetof(PoolHits, rec), hipMemcpyDeviceToHost, d_.hit_stream));
-  HIPTRY(hipStreamSynchronize(d_.hit_stream));
+  static_assert(offsetof(PoolHits, claim) == sizeof(PoolHits::n) && offsetof(PoolHits, moves) == 3 * sizeof(PoolHits::n) &&
+                    offsetof(PoolHits, rec) == 4 * sizeof(PoolHits::n),
+                "the hit and claim counters (and the best words and move counters behind them) are read with one copy");
+  // (the counters: the launch's own copy, made in stream order behind it -- Worker::launch)
+  memcpy(d_.h_hit_n, d_.h_hit_ring + (size_t)f.ring * (offsetof(PoolHits, rec) / sizeof(unsigned long long)),
+         offsetof(PoolHits, rec));
   for (const PoolInflight::Collect& c : f.collect) {
     Slot& sl = slots_[c.slot];
     if (sl.state == SlotState::kFree || sl.gen != c.gen) continue;  // (a slot keeps its job while a launch holds it)
@@ -1302,6 +1368,7 @@ void Worker::collect_best(Slot& sl, const PoolInflight::Collect& c, const PoolIn
   JobDev& jd = j.dev[sl.k];
   jd.hit_n += n;
   jd.launches++;
+  if (c.claim) jd.moves += d_.h_hit_n[3 * kMaxSlots + c.slot];  // (PoolHits::moves, read with the counters)
   j.best.records += n;
   j.best.records_max = std::max(j.best.records_max, n);
   j.best.room = j.best.room ? std::min<uint64_t>(j.best.room, c.room) : c.room;
@@ -1356,6 +1423,7 @@ void Worker::collect_sweep(Slot& sl, const PoolInflight::Collect& c, const PoolI
   const uint64_t take = std::min<uint64_t>(stored, (uint64_t)NPOW_SWEEP_JOB_HITS - jd.hits.size());
   jd.hits.insert(jd.hits.end(), d_.h_hits, d_.h_hits + take);
   jd.launches++;
+  if (c.claim) jd.moves += d_.h_hit_n[3 * kMaxSlots + c.slot];  // (PoolHits::moves, read with the counters)
   credit_entry(sl, c, f);
 }
 
@@ -1392,6 +1460,7 @@ int Worker::retire_launches() {
       if (sl.job && sl.job->max_per_dev && !sl.win_seen && sl.stop_us == 0)
         for (size_t i = 0; i < m; ++i) sl.unread += sl.inflight[i].count;
       sl.inflight.erase(sl.inflight.begin(), sl.inflight.begin() + (ptrdiff_t)m);
+      if (sl.inflight.empty()) sl.ending = false;
       // a decided job's last launch on this device has completed: the device hashes nothing more of it, so
       // its stop time is now (npow_wait_info), not when the done counts' read-back lands
       // (a slot finished from its final count has its stop time already: no pool lock for it -- a lingering launch
@@ -1475,7 +1544,7 @@ int Worker::retire_slots() {
       credit_job_locked(sl, c);
       if (j.claimed() && !j.decided && !d_.dead && c.done != sl.claimed) {
         // a claimed job: the nonces its workgroups counted are not the prefixes its launches' claims covered
-        j.err = std::string(j.is_best() ? "background best job" : "background sweep job") + ": device " +
+        j.err = std::string(j.shared ? "shared" : "background") + (j.is_best() ? " best job" : " sweep job") + ": device " +
                 std::to_string(d_.id) + " hashed " + std::to_string(c.done) +
                 " nonces where its claims cover " + std::to_string(sl.claimed);
         decide_locked(j, NPOW_ERR_INTERNAL);
@@ -1738,6 +1807,10 @@ int pool_device_init(Device& d) {
   HIPTRY(hipHostMalloc(&hn, offsetof(PoolHits, rec) + (size_t)kSweepHits * sizeof(uint64_t), hipHostMallocDefault));
   d.h_hit_n = (unsigned long long*)hn;  // (the hit counters, then the claim counters)
   d.h_hits = (uint64_t*)((char*)hn + offsetof(PoolHits, rec));
+  void* hr = nullptr;
+  HIPTRY(hipHostMalloc(&hr, (size_t)kEventRing * offsetof(PoolHits, rec), hipHostMallocDefault));
+  memset(hr, 0, (size_t)kEventRing * offsetof(PoolHits, rec));
+  d.h_hit_ring = (unsigned long long*)hr;
   return NPOW_OK;
 }
 
@@ -1752,6 +1825,7 @@ void pool_device_free(Device& d) {  // tolerates a partial pool_device_init
   for (int s = 0; s < kMaxSlots; ++s)
     if (d.ev_done[s]) (void)hipEventDestroy(d.ev_done[s]);
   if (d.h_hit_n) (void)hipHostFree(d.h_hit_n);  // (h_hits is part of it)
+  if (d.h_hit_ring) (void)hipHostFree(d.h_hit_ring);
   if (d.hit_stream) (void)hipStreamDestroy(d.hit_stream);
 }
 

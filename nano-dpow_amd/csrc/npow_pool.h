@@ -55,6 +55,8 @@ struct JobDev {
   // tables because a foreground job wanted the device, and since when it is (0 = it is not).
   uint64_t progress = 0, launches = 0, launches_cut = 0;
   double held_us = 0, held_since = 0;
+  uint64_t moves = 0;  // workgroups that came to the job's claimed entries from another entry of a running launch (the
+                       // kernel's count, PoolHits::moves, summed over the retired launches; npow_ticket_share)
 };
 
 enum class JobKind : uint8_t { kSearch, kSweep, kBest };
@@ -89,10 +91,16 @@ struct Job {
   // changes: npow_promote refuses the ticket) is a claimed job: its entries are claimed ones (kEntryClaim, beside
   // kEntryBest for a best job) and a device leaves its slot out of every table built while a foreground job is live
   // there (Worker::hold_out).
+  // Either collecting kind with `shared` set (npow_submit_sweep_shared, npow_submit_best_shared; it never changes) is
+  // a claimed job too, but a foreground one that no table leaves out: it weighs 1 in the start map of a table whose
+  // bounded entries are all claimed (pool_table_weights_claimed), and its entries take the workgroups that the searches
+  // of its launch no longer want (npow_kernel.hip ls2_move_claimed).  `background` stays false.
   JobKind kind = JobKind::kSearch;
   bool collects() const { return kind != JobKind::kSearch; }  // its entries collect records: a sweep or a best job
   bool is_best() const { return kind == JobKind::kBest; }
-  bool claimed() const { return collects() && background; }  // a collecting job of the background class
+  bool claimed() const { return collects() && (background || shared); }  // its entries are claimed ones
+  bool held_class() const { return collects() && background; }  // a collecting job of the background class (hold_out)
+  int range_class() const { return background ? 1 : shared ? 2 : 0; }  // npow_range_share_info::klass
   struct Best {  // a best job's own state (guarded by g_pool.mu)
     BestFold of;
     uint64_t records = 0;      // records read from its retired launches, and ...
@@ -107,6 +115,7 @@ struct Job {
   bool background = false;  // npow_submit_background, until npow_promote lifts it (guarded by g_pool.mu): each GPU
                             // hashes it only on workgroups no foreground job wants (PoolEntry::bg), and it is admitted
                             // behind every foreground job; weight stays 1 meanwhile.  The CPU device ignores it
+  bool shared = false;      // a collecting job of the shared class (above); set at the submit, never changes
   std::vector<int> devs;  // device ids; the k-th starts on [start + k * spacing, + stride)
   std::vector<JobDev> dev;  // per device k of devs; guarded by g_pool.mu
   uint64_t retargets = 0;           // raises of the threshold that took effect (pool_retarget)

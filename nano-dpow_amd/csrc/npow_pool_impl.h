@@ -54,6 +54,7 @@ struct Faults {
   int hip_dev = -1;           // logical device whose launches fail ...
   uint64_t hip_after = 0;     // ... after this many
   bool retarget_blind = false;  // pool_retarget writes no floor record
+  bool no_moves = false;        // NANOPOW_SHARED_NO_MOVES: launches carry kTabNoMoves (no move to a claimed entry)
 };
 const Faults& faults();  // npow_pool.cpp
 

@@ -16,6 +16,8 @@
 // the best value their launch has seen; the workers fold them into the job's best (Worker::collect_best), and
 // pool_wait_best returns it.  DESIGN.md section 1 "Best jobs".  With Job::background (npow_submit_best_background) it
 // is of the background sweep job's class, claimed entries and all.  DESIGN.md section 1 "Background best jobs".
+// Either collecting kind with Job::shared (npow_submit_sweep_shared, npow_submit_best_shared) is a foreground job with
+// claimed entries that is never held out; pool_ticket_share tells the class.  DESIGN.md section 1 "Shared range jobs".
 #include <algorithm>
 
 #include "npow_pool_impl.h"
@@ -477,11 +479,12 @@ int pool_relax(uint64_t ticket, uint64_t threshold, uint32_t* answered) {
 // launches' hits as they retire (collect_hits), and pool_wait_sweep merges the devices' lists.
 static int submit_collecting(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count,
                              uint64_t device_mask, const volatile uint32_t* cancel, uint64_t* ticket, JobKind kind,
-                             bool background) {
+                             int klass) {
   auto j = std::make_shared<Job>();
   j->kind = kind;  // (a best job: `threshold` is its floor)
-  j->background = background;  // (npow_submit_sweep_background, npow_submit_best_background: admitted as a background
+  j->background = klass == 1;  // (npow_submit_sweep_background, npow_submit_best_background: admitted as a background
                                // search is, admit_locked)
+  j->shared = klass == 2;      // (npow_submit_sweep_shared, npow_submit_best_shared: admitted as a plain job is)
   j->count = count;
   j->pre = host_precompute(root);
   npow_asm_uniforms(j->pre.m, j->u);
@@ -518,8 +521,8 @@ static int submit_collecting(const uint8_t root[32], uint64_t threshold, uint64_
 }
 
 int pool_submit_sweep(const uint8_t root[32], uint64_t threshold, uint64_t start, uint64_t count, uint64_t device_mask,
-                      const volatile uint32_t* cancel, uint64_t* ticket, bool background) {
-  return submit_collecting(root, threshold, start, count, device_mask, cancel, ticket, JobKind::kSweep, background);
+                      const volatile uint32_t* cancel, uint64_t* ticket, int klass) {
+  return submit_collecting(root, threshold, start, count, device_mask, cancel, ticket, JobKind::kSweep, klass);
 }
 
 int pool_ticket_sweep(uint64_t ticket, npow_sweep_info* out) {
@@ -588,8 +591,8 @@ int pool_wait_sweep(uint64_t ticket, int64_t timeout_us, uint64_t* out, uint64_t
 // jobs".  background (npow_submit_best_background): the class of a background sweep job -- claimed entries, held out
 // while a foreground job wants the device (Job::claimed()).
 int pool_submit_best(const uint8_t root[32], uint64_t floor, uint64_t start, uint64_t count, uint64_t device_mask,
-                     const volatile uint32_t* cancel, uint64_t* ticket, bool background) {
-  return submit_collecting(root, floor, start, count, device_mask, cancel, ticket, JobKind::kBest, background);
+                     const volatile uint32_t* cancel, uint64_t* ticket, int klass) {
+  return submit_collecting(root, floor, start, count, device_mask, cancel, ticket, JobKind::kBest, klass);
 }
 
 int pool_ticket_best(uint64_t ticket, npow_best_info* out) {
@@ -630,6 +633,31 @@ int pool_ticket_best_hold(uint64_t ticket, npow_best_hold_info* out) {
     held += jd.held_us + (jd.held_since > 0 && t > jd.held_since ? t - jd.held_since : 0.0);
   }
   out->background = j.background ? 1u : 0u;
+  out->held_us = (uint64_t)held;
+  return NPOW_OK;
+}
+
+// The class of a sweep or best job and what came with it (npow_ticket_share): plain 0, background 1, shared 2; the
+// launches, the launches cut and the time held as pool_ticket_sweep and pool_ticket_best_hold report them, and the
+// workgroups that moved to the job's claimed entries inside running launches (JobDev::moves).  DESIGN.md section 1
+// "Shared range jobs".
+int pool_ticket_share(uint64_t ticket, npow_range_share_info* out) {
+  std::lock_guard<std::mutex> g(g_pool.mu);
+  const JobP jp = ticket_job_locked(ticket);
+  if (!jp) return NPOW_ERR_BAD_ARGUMENT;
+  const Job& j = *jp;
+  if (!j.collects())
+    return fail(NPOW_ERR_BAD_ARGUMENT, std::string("npow_ticket_share: the ticket is ") + kKindWords[0][0] +
+                                           kKindWords[0][1]);
+  const double t = j.finished.load() ? j.t_finish : now_us();
+  double held = 0;
+  for (const JobDev& jd : j.dev) {
+    out->launches += jd.launches;
+    out->launches_cut += jd.launches_cut;
+    out->moves += jd.moves;
+    held += jd.held_us + (jd.held_since > 0 && t > jd.held_since ? t - jd.held_since : 0.0);
+  }
+  out->klass = (uint32_t)j.range_class();
   out->held_us = (uint64_t)held;
   return NPOW_OK;
 }

@@ -90,6 +90,98 @@ inline uint32_t pool_table_weights(const uint32_t* w, uint32_t n, uint32_t grid,
   }
 }
 
+// Tables with bounded entries (shared range jobs, npow_submit_sweep_shared).  A dense bounded entry (a bounded search,
+// a plain sweep or best job) is hashed by its own workgroups only, rank g / n of those with g % n == e (pool_load_ls),
+// so a table that holds one is dealt g % n.  A claimed entry (kEntryClaim) takes its chunks from a counter and needs
+// nothing of g % n: a table whose bounded entries are all claimed gets a start map over its jobs' weights by the rule
+// above -- a workgroup starts on every entry, a crowded table is halved, equal weights give g % n.
+//
+// Its map is not pool_start_pos: that one's discrepancy is up to two workgroups per entry, which is nothing to a
+// search's share and too much for a range job of weight 1 beside heavy searches on a small grid (13 workgroups of 128
+// where its share is 14.2).  The claimed map is exact: workgroup g takes place p = g * mult mod grid, a permutation
+// of the grid's places since mult is prime to grid, and stands at position p * csum / grid of [0, csum), so an entry
+// whose run of the cumulative weights is [a, b) starts floor or ceil of grid * (b - a) / csum workgroups, give or take
+// the one that straddles an end: within one workgroup of its share.  mult is an integer near grid / golden ratio
+// that is prime to grid (pool_claimed_mult), so consecutive workgroups still spread over the whole map (dispatch
+// order, pool_start_pos's reason), and since a prime to a grid of a multiple of 8 is odd, each XCD shard (g mod 8)
+// takes every eighth place.
+// Only the bounded kernels deal it (PoolTable::pad carries csum and mult, PoolTable::wsum stays 0: ls2_pick, which
+// the unbounded kernels share, joins the entry it is given).
+NPOW_HD inline uint32_t pool_claimed_pos(uint32_t g, uint32_t csum, uint32_t grid, uint32_t mult) {
+  return (uint32_t)((uint64_t)(uint32_t)(((uint64_t)g * mult) % grid) * csum / grid);
+}
+// (Nearest alone is not enough: places g * mult mod grid spread evenly over every stretch of workgroups only if the
+// continued fraction of mult / grid has small partial quotients -- 317 / 512 is within 0.001 of the golden ratio and
+// left an entry of share 5 with 2 of a quarter's workgroups.  So of the multipliers prime to grid within grid / 8 of
+// grid / golden ratio the one whose largest partial quotient is smallest, the nearest among equals.)
+inline uint32_t pool_claimed_mult(uint32_t grid) {
+  if (grid < 3) return 1;
+  const uint32_t a = (uint32_t)((uint64_t)grid * 0x9E3779B9u >> 32);  // grid x 0.618...
+  const uint32_t lo = a > grid / 8 + 1 ? a - grid / 8 : 1, hi = a + grid / 8 + 1 < grid ? a + grid / 8 + 1 : grid;
+  uint32_t best = 1, best_q = ~0u, best_d = ~0u;
+  for (uint32_t c = lo; c < hi; ++c) {
+    uint32_t x = grid, y = c, q = 0;  // Euclid: the quotients are the continued fraction's, x ends as the gcd
+    while (y) {
+      if (x / y > q) q = x / y;
+      const uint32_t t = x % y;
+      x = y;
+      y = t;
+    }
+    const uint32_t d = c > a ? c - a : a - c;
+    if (x == 1 && (q < best_q || (q == best_q && d < best_d))) {
+      best = c;
+      best_q = q;
+      best_d = d;
+    }
+  }
+  return best;
+}
+// PoolTable::pad of such a table: bit 0 is kTabNoMoves (npow_internal.h), bits 1..10 csum (at most 64 entries of
+// weight 8), bits 16..31 mult (grids below 2^16; a larger one is dealt g % n).
+constexpr uint32_t kTabClaimedSumShift = 1, kTabClaimedSumMask = 0x3ffu, kTabClaimedMultShift = 16;
+NPOW_HD inline uint32_t pool_claimed_pad(uint32_t csum, uint32_t mult) {
+  return (csum << kTabClaimedSumShift) | (mult << kTabClaimedMultShift);
+}
+NPOW_HD inline uint32_t pool_claimed_pad_sum(uint32_t pad) { return (pad >> kTabClaimedSumShift) & kTabClaimedSumMask; }
+NPOW_HD inline uint32_t pool_claimed_pad_mult(uint32_t pad) { return pad >> kTabClaimedMultShift; }
+
+// kind[i]: what entry i is.  Returns csum, the claimed map's modulus, or 0 for g % n (a dense entry, equal weights,
+// a grid of 2^16 workgroups or more); wsh[] and *down as pool_table_weights sets them -- the jobs' weights halved
+// *down times, floor 1, until a workgroup starts on every entry -- and for a table with a dense entry the jobs' own
+// shifts, not halved.  mult: pool_claimed_mult(grid).
+enum : uint8_t { kTableUnbounded = 0, kTableDense = 1, kTableClaimed = 2 };
+inline uint32_t pool_table_weights_claimed(const uint32_t* w, const uint8_t* kind, uint32_t n, uint32_t grid,
+                                           uint32_t mult, uint32_t* wsh, uint32_t* down) {
+  bool dense = false;
+  for (uint32_t i = 0; i < n; ++i) dense = dense || kind[i] == kTableDense;
+  *down = 0;
+  if (dense || n > 64 || grid >= (1u << 16)) {
+    for (uint32_t i = 0; i < n; ++i) wsh[i] = pool_wsh(w[i]);
+    return 0;
+  }
+  for (uint32_t k = 0;; ++k) {
+    uint32_t sum = 0, prefix[64];
+    bool equal = true;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t eff = (w[i] >> k) ? (w[i] >> k) : 1u;
+      wsh[i] = pool_wsh(eff);
+      sum += eff;
+      prefix[i] = sum;
+      equal = equal && wsh[i] == wsh[0];
+    }
+    *down = k;
+    if (equal) return 0;
+    uint64_t started = 0;  // bit i: some workgroup starts on entry i
+    for (uint32_t g = 0; g < grid; ++g) {
+      const uint32_t r = pool_claimed_pos(g, sum, grid, mult);
+      uint32_t e = 0;
+      while (e + 1 < n && prefix[e] <= r) ++e;
+      started |= 1ull << e;
+    }
+    if (started == (n == 64 ? ~0ull : (1ull << n) - 1)) return sum;
+  }
+}
+
 // Background searches (npow_submit_background): an entry is foreground (every search above) or background
 // (PoolEntry::bg).  A background entry is hashed only by workgroups no live foreground entry of its launch wants.
 //  * Effective class: a background entry counts as foreground once its slot's boost mirror carries the entry's own

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "npow_submit_reserve", "npow_ticket_reserve", "npow_relax", "npow_submit_sweep", "npow_wait_sweep",
     "npow_submit_sweep_background", "npow_ticket_sweep", "npow_submit_best", "npow_wait_best", "npow_ticket_best",
     "npow_submit_best_background", "npow_ticket_best_hold",
+    "npow_submit_sweep_shared", "npow_submit_best_shared", "npow_ticket_share",
 )
 
 
@@ -224,6 +225,32 @@ class BestHold:
         return iter((self.background, self.launches_cut, self.held_us))
 
 
+class _RangeShareStruct(ctypes.Structure):
+    """npow_range_share_info as the C ABI lays it out (npow_ticket_share)."""
+    _fields_ = [
+        ("size", ctypes.c_uint32),
+        ("klass", ctypes.c_uint32),
+        ("launches", ctypes.c_uint64),
+        ("launches_cut", ctypes.c_uint64),
+        ("held_us", ctypes.c_uint64),
+        ("moves", ctypes.c_uint64),
+    ]
+
+
+RANGE_PLAIN, RANGE_BACKGROUND, RANGE_SHARED = 0, 1, 2  # npow_range_share_info.klass
+
+
+@dataclass
+class RangeShare:
+    """The class of a sweep or best job and what came with it (SweepTicket.share, BestTicket.share,
+    npow_ticket_share)."""
+    klass: int             # RANGE_PLAIN, RANGE_BACKGROUND or RANGE_SHARED
+    launches: int          # launches that held an entry of the job, summed over its devices
+    launches_cut: int      # of those, launches a yield or the time budget ended before their span was hashed
+    held_us: int           # time the job sat admitted but left out of its devices' tables (background jobs only)
+    moves: int             # workgroups that came to the job's entry from another entry of a running launch
+
+
 @dataclass
 class BestResult:
     status: int            # NPOW_OK / NPOW_EXHAUSTED (nothing reached the floor) / NPOW_CANCELLED
@@ -367,6 +394,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             lib.npow_submit_best_background.restype = ctypes.c_int
             lib.npow_ticket_best_hold.argtypes = [u64, ctypes.POINTER(_BestHoldStruct)]
             lib.npow_ticket_best_hold.restype = ctypes.c_int
+        if hasattr(lib, "npow_submit_sweep_shared"):  # added within ABI 7: probed for
+            for f in (lib.npow_submit_sweep_shared, lib.npow_submit_best_shared):
+                f.argtypes = [u8p, u64, u64, u64, u64, p, pu64]
+                f.restype = ctypes.c_int
+            lib.npow_ticket_share.argtypes = [u64, ctypes.POINTER(_RangeShareStruct)]
+            lib.npow_ticket_share.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -593,6 +626,17 @@ class Ticket(_JobTicket):
         return lib.npow_wait(self.ticket, 10_000_000, None, None, None)
 
 
+def _range_share(t: "_JobTicket") -> RangeShare:
+    lib = t.engine.lib
+    t._need(lib, "npow_ticket_share")
+    if not t.ticket:
+        raise NanoPowError(NPOW_ERR_BAD_ARGUMENT, "the ticket is collected")
+    i = _RangeShareStruct()
+    i.size = ctypes.sizeof(_RangeShareStruct)
+    _check(lib.npow_ticket_share(t.ticket, ctypes.byref(i)), lib)
+    return RangeShare(i.klass, i.launches, i.launches_cut, i.held_us, i.moves)
+
+
 class SweepTicket(_JobTicket):
     """A submitted sweep job (npow_submit_sweep); wait() returns its SweepResult once."""
 
@@ -632,6 +676,13 @@ class SweepTicket(_JobTicket):
         _check(lib.npow_ticket_sweep(self.ticket, ctypes.byref(i)), lib)
         return SweepInfo(bool(i.background), i.count, i.nonces_done, i.hits, i.launches, i.launches_cut, i.held_us,
                          bool(i.finished))
+
+    def share(self) -> RangeShare:
+        """The job's class (plain, background, shared), its launches, the launches cut, the time held out and the
+        workgroups that moved to it inside running launches (npow_ticket_share); never waits for a GPU.
+        NanoPowError(NPOW_ERR_BAD_ARGUMENT) once the ticket is collected, or when the loaded library has no
+        npow_ticket_share."""
+        return _range_share(self)
 
     def _collect_abandoned(self, lib) -> int:
         return lib.npow_wait_sweep(self.ticket, 10_000_000, None, 0, ctypes.byref(ctypes.c_uint64(0)), None)
@@ -684,6 +735,13 @@ class BestTicket(_JobTicket):
         i.size = ctypes.sizeof(_BestHoldStruct)
         _check(lib.npow_ticket_best_hold(self.ticket, ctypes.byref(i)), lib)
         return BestHold(i.background, i.launches_cut, i.held_us)
+
+    def share(self) -> RangeShare:
+        """The job's class (plain, background, shared), its launches, the launches cut, the time held out and the
+        workgroups that moved to it inside running launches (npow_ticket_share); never waits for a GPU.
+        NanoPowError(NPOW_ERR_BAD_ARGUMENT) once the ticket is collected, or when the loaded library has no
+        npow_ticket_share."""
+        return _range_share(self)
 
     def _collect_abandoned(self, lib) -> int:
         n, v = ctypes.c_uint64(0), ctypes.c_uint64(0)
@@ -829,14 +887,20 @@ class Engine:
 
     def submit_sweep(self, root: bytes, threshold: int, start: int, count: int, device_mask: int = 0,
                      cancel: Optional[CancelToken] = None, cap: int = 1 << 16, *,
-                     background: bool = False) -> SweepTicket:
+                     background: bool = False, shared: bool = False) -> SweepTicket:
         """Queue a sweep job and return at once (npow_submit_sweep): every hit of [start, start + count) enumerated
         inside the work pool's launches, beside the live searches, where sweep() takes the devices from the pool.
         SweepTicket.wait collects up to `cap` hits.  Keep `cancel` alive until then (the ticket holds a reference).
         background=True (npow_submit_sweep_background): each GPU hashes the job only while no foreground job wants
         it, and a search that arrives waits one short chunk; continuous foreground load starves the job.
+        shared=True (npow_submit_sweep_shared): the job takes a weight-1 share of each GPU beside the searches and
+        the workgroups they no longer want, is never held out, and a search that arrives waits one short chunk;
+        SweepTicket.share tells the class and the moves.  ValueError with background=True as well.
         NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the loaded library lacks the call."""
-        name = "npow_submit_sweep_background" if background else "npow_submit_sweep"
+        if shared and background:
+            raise ValueError("a range job is shared or background, not both")
+        name = ("npow_submit_sweep_shared" if shared else
+                "npow_submit_sweep_background" if background else "npow_submit_sweep")
         _JobTicket._need(self.lib, name)
         t = ctypes.c_uint64(0)
         _check(getattr(self.lib, name)(_root(root), threshold & M64, start & M64, count, device_mask,
@@ -844,7 +908,8 @@ class Engine:
         return SweepTicket(self, t.value, cancel, cap)
 
     def submit_best(self, root: bytes, start: int, count: int, floor: int = 0, device_mask: int = 0,
-                    cancel: Optional[CancelToken] = None, background: bool = False) -> BestTicket:
+                    cancel: Optional[CancelToken] = None, background: bool = False,
+                    shared: bool = False) -> BestTicket:
         """Queue a best job and return at once (npow_submit_best): the nonce of [start, start + count) with the
         highest work value, found inside the work pool's launches beside the live searches -- exact at any floor
         (only values >= floor are candidates; 0 allowed).  BestTicket.wait gives status, nonce, value, nonces_done.
@@ -852,8 +917,14 @@ class Engine:
         background=True (npow_submit_best_background): each GPU hashes the job only while no foreground job wants
         it, and a search that arrives waits one short chunk; the best so far (BestTicket.info) survives every
         interruption; continuous foreground load starves the job.  BestTicket.hold tells what the class cost.
+        shared=True (npow_submit_best_shared): the job takes a weight-1 share of each GPU beside the searches and
+        the workgroups they no longer want, is never held out, and a search that arrives waits one short chunk;
+        BestTicket.share tells the class and the moves.  ValueError with background=True as well.
         NanoPowError(NPOW_ERR_BAD_ARGUMENT) when the loaded library lacks the call."""
-        name = "npow_submit_best_background" if background else "npow_submit_best"
+        if shared and background:
+            raise ValueError("a range job is shared or background, not both")
+        name = ("npow_submit_best_shared" if shared else
+                "npow_submit_best_background" if background else "npow_submit_best")
         _JobTicket._need(self.lib, name)
         t = ctypes.c_uint64(0)
         _check(getattr(self.lib, name)(_root(root), floor & M64, start & M64, count, device_mask,

@@ -61,7 +61,11 @@ it, in place (npow_relax: decided at once from its reserve when that qualifies).
 (a JSON boolean, as ``work_generate``'s) it is a background best job
 (npow_submit_best_background): the GPUs hash it only while no foreground request wants
 them, so a long one can run beside ``work_generate`` traffic -- and makes no progress
-while that traffic is continuous.  The reply is the same.
+while that traffic is continuous.  With ``"shared": true`` it is a shared best job
+(npow_submit_best_shared): it takes a weight-1 share of each GPU beside the searches and the
+workgroups they no longer want, so it finishes under continuous traffic, and a search that
+arrives waits about 0.3 ms for it, not a launch.  Both flags together are refused
+(``{"error": "Bad shared", ...}``).  The reply is the same.
 The reference serves one request at a time; here up to ``max_active`` queued
 requests are handed to libnanopow's work pool at once (npow_submit), where
 every selected GPU searches all of them in the same kernel launches, so a
@@ -413,12 +417,15 @@ class WorkServer:
         when absent) is the range's first nonce and ``"difficulty"`` a floor below which nothing is returned
         (``{"error": "Exhausted"}``).  The job queues in the engine like a bounded search; it is not shared with
         other requests, and a work_cancel of the hash cancels it.  ``"background": true`` (a JSON boolean) makes it a
-        background best job (npow_submit_best_background): hashed only while no foreground job wants the GPUs.  The
-        keyword is passed to the engine only when it is set, as work_generate's is."""
+        background best job (npow_submit_best_background): hashed only while no foreground job wants the GPUs;
+        ``"shared": true`` a shared one (npow_submit_best_shared): a weight-1 share of each GPU beside the searches,
+        never held out.  Both together are refused.  Either keyword is passed to the engine only when it is set, as
+        work_generate's is."""
         root = W.parse_hash(req)
         count = W.parse_best_count(req)
         start = W.parse_start(req)
         background = W.parse_background(req)
+        shared = W.parse_shared(req)
         floor = W.parse_threshold(req["difficulty"]) if req.get("difficulty") is not None else 0
         if start is None:
             start = self.rng.getrandbits(64)
@@ -430,7 +437,7 @@ class WorkServer:
             self._best.append(entry)
         try:
             t0 = time.perf_counter()
-            extra = {"background": True} if background else {}
+            extra = {"background": True} if background else {"shared": True} if shared else {}
             ticket = self.engine.submit_best(root, start, count, floor=floor, device_mask=self.device_mask,
                                              cancel=cancel, **extra)
             status, nonce, value, done = ticket.wait()

@@ -148,6 +148,20 @@ def parse_background(req: Dict[str, Any]) -> bool:
     return b
 
 
+def parse_shared(req: Dict[str, Any]) -> bool:
+    """The optional ``"shared"`` of a work_best request (a JSON boolean; this server's extension): the best job takes a
+    weight-1 share of each GPU beside the searches and is never held out (npow_submit_best_shared).  False when
+    absent; together with ``"background": true`` the request is refused."""
+    s = req.get("shared")
+    if s is None:
+        return False
+    if not isinstance(s, bool):
+        raise RequestError("Bad shared", "Expecting true or false")
+    if s and parse_background(req):
+        raise RequestError("Bad shared", "Expecting shared or background, not both")
+    return s
+
+
 def parse_weight(req: Dict[str, Any]) -> int:
     """The optional ``"weight"`` of a work_generate or work_promote request (an integer or a decimal string; this server's
     extension -- the reference has no such field): the request's share of each GPU among the searches in
