@@ -7,6 +7,7 @@
 #include "npow_blake2b.h"
 #include "npow_weights.h"
 #include "npow_claims.h"
+#include "npow_dense.h"
 #include "npow_hash_asm.inc"
 #include "npow_hash_asm_lockstep_ld.inc"
 
@@ -18,6 +19,7 @@ constexpr int kBlock = 256;               // npow_values_kernel_seq / npow_pairs
 // and +1.2 % sweep rate, profiles/r03_ab_wgsize*.jsonl; 256-lane ones are slower).
 constexpr int kLsWaves = 8;                // waves per workgroup (2 per SIMD) ...
 constexpr int kLsBlock = kLsWaves * 64;    // ... 512 lanes
+static_assert(kDenseWaves == (uint32_t)kLsWaves, "npow_dense.h: one block per wave of a workgroup");
 constexpr int kLsGroups = 4;               // ... four workgroups per CU: 8 waves per SIMD, 64 VGPRs each
 
 // One-root tasks (launch_task): npow_sweep_kernel_ls2 (kSweep), npow_values_kernel_ls2 (kValues, the
@@ -405,10 +407,9 @@ struct PoolShape {
   uint32_t units() const { return (uint32_t)grid; }
   // nonces a bounded entry e of n can cover in one launch of `iters` wave iterations
   uint64_t own(uint32_t e, uint32_t n, uint32_t iters) const {
-    const uint32_t U = units();
-    return (uint64_t)(U / n + (e < U % n ? 1u : 0u)) * kLsWaves * iters * 64;
+    return dense_own(units(), n, e, iters);
   }
-  uint64_t full(uint32_t iters) const { return (uint64_t)units() * kLsWaves * iters * 64; }
+  uint64_t full(uint32_t iters) const { return dense_full(units(), iters); }
   // The iteration cap of a launch: with 8 waves per SIMD a wave iteration takes as long
   // as two hashes of its SIMD's other group, so half of g_iters keeps a launch's longest duration
   // (and its nonce span) where the round-1 tuning put it.

@@ -303,15 +303,15 @@ __device__ __forceinline__ void pool_load_ls(const PoolEntry* __restrict__ pe, P
   c.slot = pe->slot;
   c.bounded = pe->bounded;
   if (pe->bounded) {
-    // own workgroups only: rank r = g / n of cnt; count <= K * iters * 64 (host: launch())
-    const uint32_t cnt = G / n + (e < G % n ? 1u : 0u);
-    const uint32_t j0 = (g / n) * kLsWaves;
+    // own workgroups only (npow_dense.h): rank g / n of the entry's; count <= K * iters * 64 (host: dense_own)
+    const uint32_t cnt = dense_groups(G, n, e);
+    const uint32_t j0 = dense_first_slot(g, n);
     c.K = kLsWaves * cnt;
     c.j = j0 + wv;
-    const uint32_t blocks = (uint32_t)((pe->count + 63) / 64);
-    c.it_end = blocks > j0 ? (blocks - j0 + c.K - 1) / c.K : 0u;  // the workgroup's first wave's count
-    c.last_b = blocks - 1u;
-    c.tail = (uint32_t)(pe->count - (uint64_t)(blocks - 1u) * 64);
+    const uint32_t blocks = dense_blocks(pe->count);
+    c.it_end = dense_it_end(blocks, j0, c.K);  // the workgroup's first wave's count
+    c.last_b = dense_last_b(blocks);
+    c.tail = dense_tail(pe->count, c.last_b);
   } else {
     c.K = G * kLsWaves;
     c.j = g * kLsWaves + wv;
@@ -1288,6 +1288,9 @@ __device__ __forceinline__ void pool_body_ls2(const PoolTable* __restrict__ tab,
       pc += kPollStride;
       bool hit = value >= thr;
       if constexpr (BOUNDED) {
+        // (npow_dense.h dense_block_lanes, written out: through the inline function the compiler swaps the operands
+        // of one s_and_b64 of this kernel, and the kernel's text is kept as it was; tests/test_dense_cpu.py holds the
+        // two together)
         const uint32_t in_lanes = b < c.last_b ? 64u : (b == c.last_b ? c.tail : 0u);
         hit = hit && lane < in_lanes;
         done += in_lanes;
