@@ -48,9 +48,13 @@ def counters(eng, devices):
     return [{k: getattr(eng.stats(d), k) for k in COUNTERS} for d in devices]
 
 
-def sole_search(eng, sh, pos, mask=1, start_shift=0):
-    """One unbounded search whose first window has its only hit at `pos`.  Returns what went wrong, or None."""
-    t = eng.submit(sh.root, sh.threshold, start=(sp.start_of(sh, pos) - start_shift) & M64, device_mask=mask)
+def sole_search(eng, sh, pos, mask=1, start_shift=0, threshold=None):
+    """One unbounded search whose first window has its only hit at `pos`.  Returns what went wrong, or None.
+    threshold: another one that h alone meets, in (sh.second, value(h)] (tests/threshold_ladder.py); the search must
+    still return h with value(h)."""
+    T = sh.threshold if threshold is None else threshold
+    assert sh.second < T <= sh.threshold
+    t = eng.submit(sh.root, T, start=(sp.start_of(sh, pos) - start_shift) & M64, device_mask=mask)
     info = t.wait_info(60)
     if info is None:
         t.cancel()
@@ -60,19 +64,20 @@ def sole_search(eng, sh, pos, mask=1, start_shift=0):
           0 < info.nonces_done <= sh.full * info.n_devices and info.nonces_done % 64 == 0)
     if ok:
         return None
-    return {"anchor": sh.anchor, "pos": pos, "coords": sp.coords_of(pos, sh.grid), "status": info.status,
-            "nonce": f"{info.nonce:016x}", "want": f"{sh.h:016x}", "value": f"{info.value:016x}",
+    return {"anchor": sh.anchor, "pos": pos, "coords": sp.coords_of(pos, sh.grid), "T": f"{T:016x}",
+            "status": info.status, "nonce": f"{info.nonce:016x}", "want": f"{sh.h:016x}", "value": f"{info.value:016x}",
             "nonces_done": info.nonces_done, "winner_device": info.winner_device}
 
 
-def copies_in_one_table(eng, sh, pos, n, hold_root):
+def copies_in_one_table(eng, sh, pos, n, hold_root, threshold=None):
     """n identical searches adopted into ONE table of exactly those n entries (device 0).  A legacy sweep of 2^33
     nonces holds the device meanwhile (npow_host.h TaskLock; ~0.25 s): the pool worker adopts the first search when
     it is submitted, then waits for the device's lock (Worker::run); when the sweep returns, Worker::step adopts the
     others -- nothing is in flight, so none becomes a dynamic entry and nothing is yielded (Worker::adopt, dyn_add,
     yield_if_long) -- and Worker::launch builds one table of every active slot (build_table).  The sweep is known to
     hold the lock once one of its launches has retired, and to have held it through the last submit if it still
-    runs then.  Returns (results, counter deltas)."""
+    runs then.  threshold: the copies' threshold where it is not value(h).  Returns (results, counter deltas)."""
+    T = sh.threshold if threshold is None else threshold
     before = eng.stats(0)
     th = threading.Thread(target=eng.sweep_result, args=(hold_root, M64, 1 << 50, 1 << 33), kwargs={"device_mask": 1})
     th.start()
@@ -83,7 +88,7 @@ def copies_in_one_table(eng, sh, pos, n, hold_root):
             assert time.monotonic() < deadline and th.is_alive(), "the sweep that holds the device never started"
             time.sleep(0.0005)
         c0 = counters(eng, [0])[0]
-        tickets = [eng.submit(sh.root, sh.threshold, start=sp.start_of(sh, pos), device_mask=1) for _ in range(n)]
+        tickets = [eng.submit(sh.root, T, start=sp.start_of(sh, pos), device_mask=1) for _ in range(n)]
         held = th.is_alive()
     finally:
         th.join()

@@ -33,7 +33,7 @@ ITERS = 16      # ... that is 16 wave iterations per launch (PoolShape::launch_i
 MAX_SEEDS = 32
 ANCHORS = ("plain", "carry32", "wrap64")
 
-SoleHit = namedtuple("SoleHit", "grid anchor seed root base h threshold full boundary")
+SoleHit = namedtuple("SoleHit", "grid anchor seed root base h threshold full boundary second")
 
 
 def full(grid, iters=ITERS):
@@ -75,14 +75,15 @@ def anchor_base(anchor, F):
 
 
 @functools.lru_cache(maxsize=None)
-def sole_hit(grid, anchor, iters=ITERS):
-    """The first seed k whose root has a unique maximum in the middle third of the 3 F values from the anchor on --
-    for the carry anchors in its second half, at or past the boundary.  A condition, not a measurement: at most
-    MAX_SEEDS seeds."""
+def sole_hit(grid, anchor, iters=ITERS, first_seed=0):
+    """The first seed k >= first_seed whose root has a unique maximum in the middle third of the 3 F values from the
+    anchor on -- for the carry anchors in its second half, at or past the boundary.  A condition, not a measurement: at
+    most MAX_SEEDS seeds.  `second` is the next lower of the 3 F values (tests/threshold_ladder.py: any threshold above
+    it and up to value(h) keeps h the only hit)."""
     F = full(grid, iters)
     base, boundary = anchor_base(anchor, F)
     lo = F if boundary is None else 3 * F // 2
-    for k in range(MAX_SEEDS):
+    for k in range(first_seed, MAX_SEEDS):
         root = root_of(k)
         v = oracle.work_values_range(root, base, 3 * F)
         off = int(v.argmax())
@@ -91,8 +92,10 @@ def sole_hit(grid, anchor, iters=ITERS):
             continue
         h = (base + off) & M64
         assert oracle.work_value_hashlib(root, h) == t, "the oracle's two restatements differ"
-        return SoleHit(grid, anchor, k, root, base, h, t, F, boundary)
-    raise AssertionError(f"no seed below {MAX_SEEDS} has its unique maximum in the middle third (grid {grid}, {anchor})")
+        v[off] = 0  # (the array is this call's own; values of one dtype compare exactly)
+        return SoleHit(grid, anchor, k, root, base, h, t, F, boundary, int(v.max()))
+    raise AssertionError(f"no seed from {first_seed} to {MAX_SEEDS - 1} has its unique maximum in the middle third "
+                         f"(grid {grid}, {anchor})")
 
 
 def carried(sh, pos):

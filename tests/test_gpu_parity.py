@@ -112,6 +112,42 @@ def test_value_ranges_vs_oracle(gpu_engine, path, start, count):
     assert got.tolist() == want.tolist()
 
 
+@pytest.mark.parametrize("start,count", [
+    (0xffffffff - 1000, 5000), ((1 << 64) - 3000, 6000), (12345, 1), (7, 65), (99, 64 * 1000 + 17)])
+def test_value_ranges_generic_path_vs_oracle(gpu_engine, start, count):
+    """NPOW_PATH_GENERIC through npow_values_path -- plain HIP C++ of the 12 rounds, one nonce per lane -- over the
+    ragged and boundary ranges of test_value_ranges_vs_oracle: a single value, partial blocks, the 2^32 carry into the
+    nonce's high word and the 2^64 wrap."""
+    rng = random.Random(start ^ count)
+    root = bytes(rng.getrandbits(8) for _ in range(32))
+    got = gpu_engine.values_array(root, start, count, path=_lib.NPOW_PATH_GENERIC)
+    want = oracle.work_values_range(root, start, count)
+    assert got.tolist() == want.tolist()
+    assert int(got[count - 1]) == oracle.work_value_hashlib(root, start + count - 1)
+
+
+PAIR_EDGES = ((1 << 32) - 1, 1 << 32, (1 << 64) - 1)
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257, 1000])
+def test_values_pairs_ragged_counts(gpu_engine, n):
+    """npow_values_pairs at counts that are no multiple of its block of 256 (and of a wave), against hashlib: a root
+    and a nonce of its own in every lane, the nonces 2^32 - 1, 2^32 and 2^64 - 1 in the first, the middle and the last
+    lane (as many as n has room for, a different one last from one n to the next)."""
+    import hashlib
+    roots = [hashlib.blake2b(b"nanopow-pairs" + (n * 4096 + i).to_bytes(8, "little"), digest_size=32).digest()
+             for i in range(n)]
+    rng = random.Random(n)
+    nonces = [((rng.getrandbits(64) | (1 << 40)) + i) & M64 for i in range(n)]
+    lanes = sorted({0, n // 2, n - 1})
+    for k, lane in enumerate(reversed(lanes)):
+        nonces[lane] = PAIR_EDGES[(n + 2 - k) % 3]
+    assert len(set(nonces)) == n == len(set(roots))
+    assert nonces[n - 1] in PAIR_EDGES and (n < 3 or set(PAIR_EDGES) <= set(nonces))
+    want = [oracle.work_value_hashlib(r, x) for r, x in zip(roots, nonces)]
+    assert gpu_engine.values_pairs(roots, nonces) == want
+
+
 def test_value_range_2p24_both_streams(gpu_engine):
     """2^24 consecutive values (one full values launch) through both generated streams, equal to
     each other and to the oracle's on every nonce."""
