@@ -334,7 +334,9 @@ int npow_promote(uint64_t ticket, uint32_t weight);
  * the job's threshold becomes max(current, threshold) -- this call never lowers it (npow_relax does, for a search
  * with a reserve), and a threshold at or below the current one is NPOW_OK with no effect.  Nothing ends or restarts: the search keeps its slot, its weight and its place in the
  * nonce space on every device of a split job, the GPUs pass over hits that no longer qualify (npow_search_info
- * stale_hits) and the CPU workers compare with the current threshold.  After NPOW_OK every result the ticket returns
+ * stale_hits) and the CPU workers compare with the current threshold.  A search with a reserve (npow_submit_reserve)
+ * passes over them too: until the running launch ends, the hits between the old threshold and the new one do not
+ * reach its reserve.  After NPOW_OK every result the ticket returns
  * has value >= threshold.  NPOW_TOO_LATE when the search was already decided, cancelled or finished (not yet
  * collected): its result stands and may be below `threshold`.  NPOW_ERR_BAD_ARGUMENT for an unknown or collected
  * ticket.  Bounded searches are accepted: the threshold does not touch their coverage.  Never waits for a GPU. */
@@ -343,7 +345,11 @@ int npow_retarget(uint64_t ticket, uint64_t threshold);
 /* Queue a search with a reserve threshold (added within ABI 7; probe for the symbol): an unbounded search, as
  * npow_submit_weighted with max_nonces_per_device = 0 -- a background one with background != 0, as
  * npow_submit_background (its weight then only checked) -- that also remembers, on each GPU, the best nonce it has
- * passed whose value is in [reserve, threshold): its reserve.  The hot loop is the same (it compares with `reserve`
+ * passed whose value is in [reserve, threshold): its reserve.  `threshold` is the current one, with one exception:
+ * in the launch that is running when npow_retarget raises the search, the values between the threshold that
+ * launch's entry was built with and the raised one are counted as stale hits and are NOT kept (a later npow_relax to
+ * a level among them is lowered in place, not answered at once); every later launch keeps them.  The hot loop is
+ * the same (it compares with `reserve`
  * and sorts the rare hits afterwards), so the reserve costs nothing per nonce.  npow_ticket_reserve looks at it,
  * npow_relax lowers the search's threshold to any level down to `reserve`.  reserve == threshold is npow_submit_weighted
  * / npow_submit_background itself.  NPOW_ERR_BAD_ARGUMENT for reserve > threshold, reserve < NPOW_RESERVE_MIN and a

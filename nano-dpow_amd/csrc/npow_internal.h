@@ -8,6 +8,7 @@
 #include "npow_weights.h"
 #include "npow_claims.h"
 #include "npow_dense.h"
+#include "npow_reserve_key.h"
 #include "npow_hash_asm.inc"
 #include "npow_hash_asm_lockstep_ld.inc"
 
@@ -297,13 +298,7 @@ struct PoolDevState {
   // Sweep jobs: the hit records of the launches in flight (PoolHits above; 2 x 8 MiB).  Last: nothing above moves.
   alignas(64) PoolHits hits[2];
 };
-// The key of a reserve candidate: the slot's generation above 24 bits of the value.  Reserve thresholds are at least
-// NPOW_RESERVE_MIN (fffff00000000000), so a candidate's top 20 bits are ones and bits 43..20 order candidates to one
-// part in 2^24 of that range; two that tie there are as good as each other.  Generations stay below 2^40 (one per
-// adoption: centuries at any rate a GPU can be armed).
-__host__ __device__ inline unsigned long long pool_reserve_key(uint64_t gen, uint64_t value) {
-  return (unsigned long long)((gen << 24) | ((value >> 20) & 0xffffffull));
-}
+// (pool_reserve_key, the key of a reserve candidate: npow_reserve_key.h)
 
 // Pinned host-coherent mailbox of the pool: one win record per slot (the winner stores
 // nonce and value, then releases gen) and one kill word per slot the host raises.

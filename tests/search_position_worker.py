@@ -69,15 +69,20 @@ def sole_search(eng, sh, pos, mask=1, start_shift=0, threshold=None):
             "nonces_done": info.nonces_done, "winner_device": info.winner_device}
 
 
-def copies_in_one_table(eng, sh, pos, n, hold_root, threshold=None):
+def copies_in_one_table(eng, sh, pos, n, hold_root, threshold=None, reserve=None, watch=None):
     """n identical searches adopted into ONE table of exactly those n entries (device 0).  A legacy sweep of 2^33
     nonces holds the device meanwhile (npow_host.h TaskLock; ~0.25 s): the pool worker adopts the first search when
     it is submitted, then waits for the device's lock (Worker::run); when the sweep returns, Worker::step adopts the
     others -- nothing is in flight, so none becomes a dynamic entry and nothing is yielded (Worker::adopt, dyn_add,
     yield_if_long) -- and Worker::launch builds one table of every active slot (build_table).  The sweep is known to
     hold the lock once one of its launches has retired, and to have held it through the last submit if it still
-    runs then.  threshold: the copies' threshold where it is not value(h).  Returns (results, counter deltas)."""
+    runs then.  threshold: the copies' threshold where it is not value(h).  Returns (results, counter deltas).
+    reserve: the copies' reserve threshold (tests/reserve_exact_worker.py); watch(tickets) is then called once the
+    sweep has returned and all n are submitted -- it must leave every copy decided or cancelled -- and what it returns
+    is the third item of the result."""
     T = sh.threshold if threshold is None else threshold
+    kw = {} if reserve is None else {"reserve": reserve}
+    watched = None
     before = eng.stats(0)
     th = threading.Thread(target=eng.sweep_result, args=(hold_root, M64, 1 << 50, 1 << 33), kwargs={"device_mask": 1})
     th.start()
@@ -88,19 +93,28 @@ def copies_in_one_table(eng, sh, pos, n, hold_root, threshold=None):
             assert time.monotonic() < deadline and th.is_alive(), "the sweep that holds the device never started"
             time.sleep(0.0005)
         c0 = counters(eng, [0])[0]
-        tickets = [eng.submit(sh.root, T, start=sp.start_of(sh, pos), device_mask=1) for _ in range(n)]
+        tickets = [eng.submit(sh.root, T, start=sp.start_of(sh, pos), device_mask=1, **kw) for _ in range(n)]
         held = th.is_alive()
     finally:
         th.join()
-        deadline = time.monotonic() + 30  # (for all of them: a copy that has not ended then is cancelled)
-        results = [t.wait(max(0.0, deadline - time.monotonic())) for t in tickets]
-        for t, r in zip(tickets, results):
-            if r is None:
-                t.cancel()
-                t.wait(30)
+        try:
+            if watch is not None and len(tickets) == n:
+                watched = watch(tickets)
+        except BaseException:
+            for t in tickets:
+                t.cancel()  # (a watch that failed half-way leaves no endless copy behind)
+            raise
+        finally:
+            deadline = time.monotonic() + 30  # (for all of them: a copy that has not ended then is cancelled)
+            results = [t.wait(max(0.0, deadline - time.monotonic())) for t in tickets]
+            for t, r in zip(tickets, results):
+                if r is None:
+                    t.cancel()
+                    t.wait(30)
     assert held, "the sweep ended before the last search was submitted"
     c1 = counters(eng, [0])[0]
-    return results, {k: c1[k] - c0[k] for k in COUNTERS}
+    deltas = {k: c1[k] - c0[k] for k in COUNTERS}
+    return (results, deltas) if watch is None else (results, deltas, watched)
 
 
 def main():
